@@ -34,8 +34,19 @@ def test_every_detector_cfg_is_present():
     assert len(NAMES) == 25 and set(NAMES) <= set(available_netdefs())
 
 
+@pytest.fixture
+def fixture_threads():
+    """The train-mode heads at this size normalise over a handful of values per channel, which amplifies the fp32
+    summation order of the CPU convolutions -- and that order follows the intra-op thread count (1 or 16 threads instead
+    of 8 move the deepest cfgs by percents).  allcfg.npz was recorded with 8 threads: the oracle runs with as many."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 @pytest.mark.parametrize("name", NAMES)
-def test_oracle_matches_reference_heads(name):
+def test_oracle_matches_reference_heads(name, fixture_threads):
     net = _oracle(name)
     sd = net.synth_state(seed=0)
     x, y = _inputs()
