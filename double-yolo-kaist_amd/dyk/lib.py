@@ -17,6 +17,7 @@ EW_ACCUM = 1
 EW_SKIP = 2
 MAX_TAPS = 25
 SE_POOL_SPLITS = 16        # DYK_SE_POOL_SPLITS (include/dyk_hip.h): partial-sum planes of the pixel-split SE pool
+EMA_MAX_REGIONS = 4        # DYK_EMA_MAX_REGIONS (include/dyk_hip.h): regions of one dyk_ema_update launch
 
 # op codes of DykCommand (include/dyk_hip.h)
 (OP_CONV, OP_WGRAD, OP_BN_FINALIZE, OP_BN_ACT_FWD, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY, OP_AXPBY, OP_DOT,
@@ -176,6 +177,11 @@ class DykOptimDesc(ctypes.Structure):
                 ("zero_grad", _i32)]
 
 
+class DykEmaDesc(ctypes.Structure):
+    _fields_ = [("src", _vp * EMA_MAX_REGIONS), ("dst", _vp * EMA_MAX_REGIONS), ("n", _i64 * EMA_MAX_REGIONS),
+                ("nregions", _i32), ("d", _f32), ("omd", _f32)]
+
+
 class DykNmsDesc(ctypes.Structure):
     _fields_ = [("pred", _vp), ("out", _vp), ("out_rows", _vp), ("counts", _vp), ("ws", _vp), ("ws_per_image", _i64),
                 ("B", _i32), ("N", _i32), ("no", _i32), ("conf_thres", _f32), ("iou_thres", _f32),
@@ -251,6 +257,7 @@ SIGNATURES = {
     "dyk_nms": (_i32, [_P(DykNmsDesc), _vp]),
     "dyk_adam_step": (_i32, [_P(DykOptimDesc), _vp]),
     "dyk_sgd_step": (_i32, [_P(DykOptimDesc), _vp]),
+    "dyk_ema_update": (_i32, [_P(DykEmaDesc), _vp]),
     "dyk_run_commands_timed": (_i32, [_P(DykCommand), _i32, _vp, _P(_f32)]),
     "dyk_loss_scale_grads": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "dyk_loss_scale_grads3": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),

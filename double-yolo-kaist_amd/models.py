@@ -3,6 +3,7 @@ YOLOLayer, YOLO, load_darknet_weights; reference models.py:7-364), same module-l
 state_dict key names, but YOLO.forward executes a compiled native plan (dyk/plan.py, dyk/engine.py)
 instead of walking the module list in Python.
 """
+import copy
 import math
 
 import numpy as np
@@ -172,6 +173,20 @@ class YOLO(nn.Module):
             from dyk.engine import Engine
             object.__setattr__(self, "_engine", Engine(self))
         return self._engine
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy (ModelEMA, reference torch_utils.py:98): the module tree and copies of the parameter and buffer values
+        on the same device, without the engine.  Its ParamStore and plans hold raw device addresses of THIS model's flat buffers
+        and arenas (the parameters and BatchNorm buffers are views into them), and the `_dyk_*` attributes hold the loss's
+        per-model runtime state (pending flag copies and their events, dyk/detect.py): none of it is copied.  The copy gets
+        compact tensors of its own, adopts its own flat buffers and compiles its own plans at its first forward pass."""
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for b in self.buffers():              # (torch would copy the whole flat buffer a view lives in)
+            memo.setdefault(id(b), b.detach().clone())
+        state = {k: (None if k == "_engine" else v) for k, v in self.__dict__.items() if not k.startswith("_dyk_")}
+        new.__setstate__(copy.deepcopy(state, memo))
+        return new
 
     def forward(self, x, y=None):
         """x: visible batch f32 [B,3,H,W] in 0..1, y: LWIR batch or None.

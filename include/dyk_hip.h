@@ -767,6 +767,26 @@ int dyk_adam_step(const DykOptimDesc* desc, void* stream);
 int dyk_sgd_step(const DykOptimDesc* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Exponential moving average of the flat buffers (replaces the per-entry loop of ModelEMA.update, reference
+ * build_utils/torch_utils.py:108-120: `v *= d; v += (1. - d) * msd[k]` over every floating state_dict entry).
+ * One launch for up to DYK_EMA_MAX_REGIONS regions (the parameter store P and the running statistics R):
+ *   dst[r][i] = fl32(fl32(dst[r][i] * d) + fl32(omd * src[r][i]))    i < n[r]
+ * two roundings per product and one per sum, no FMA: bit-identical to torch's fp32 ops, NaN / Inf included.
+ *   d   : the decay rounded to fp32;  omd : (1 - decay) formed in double, then rounded to fp32
+ * Every n[r] a positive multiple of 4, every pointer 16-byte aligned, 1 <= nregions <= DYK_EMA_MAX_REGIONS; otherwise
+ * DYK_ERR_ARG before any launch.
+ * ---------------------------------------------------------------------------------- */
+#define DYK_EMA_MAX_REGIONS 4
+typedef struct DykEmaDesc {
+    const float* src[DYK_EMA_MAX_REGIONS];   /* the live model's buffers (read) */
+    float* dst[DYK_EMA_MAX_REGIONS];         /* the shadow's buffers (read, written) */
+    int64_t n[DYK_EMA_MAX_REGIONS];
+    int32_t nregions;
+    float d, omd;
+} DykEmaDesc;
+int dyk_ema_update(const DykEmaDesc* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Stem convolution (Cin = 3, 3x3, pad 1, stride 1 | 2, Cout 16 | 32) straight from the image batch, no im2col.
  * Replaces `imgs.float() / 255.0` (train_utils/kaist_train_eval_utils.py:54-55, evaluate.py:67-68) + nn.Conv2d(3, C, 3)
  * of module_list[0] / module_list[second_index] (models.py:34-42) and that layer's weight gradient.
