@@ -172,6 +172,10 @@ class _FusedBase(torch.optim.Optimizer):
         d.mask = mask.data_ptr() if mask is not None else None
         bf = st._compute.get(torch.bfloat16)
         d.wc = bf["Wc"].data_ptr() if bf is not None else None
+        # the kernel writes the bf16 copy of the elements it updates and skips frozen ones: their copy is still right afterwards
+        # only if it was current when the step began (a frozen tensor overwritten since the last forward -- load_state_dict,
+        # load_darknet_weights -- needs the full cast).  Without a mask every element is written.
+        self._wc_complete = bf is not None and (mask is None or bf["version"] == st.version_key())
         return d, bf
 
     def _check_loss_flag(self):
@@ -188,7 +192,7 @@ class _FusedBase(torch.optim.Optimizer):
         st.mark_dirty()
         if bf is not None:                # the bf16 copy was written by the step kernel: refresh the rest only
             side = self._side
-            st.compute_weights(torch.bfloat16, skip_cast=True, side=side)
+            st.compute_weights(torch.bfloat16, skip_cast=self._wc_complete, side=side)
         for dt in list(st._compute):
             if dt != torch.bfloat16:
                 st.compute_weights(dt)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import C1, C3, hyp, oracle_net
+from helpers import C1, C3, C5, hyp, oracle_net
 
 pytestmark = pytest.mark.gpu
 
@@ -115,6 +115,66 @@ def test_freeze_layers_like_the_reference_harness():
         assert changed > 0
         # BatchNorm of frozen layers still runs in train mode (running statistics move), as in the reference
         assert not torch.equal(sd1["module_list.0.BatchNorm2d.running_mean"], sd0["module_list.0.BatchNorm2d.running_mean"])
+
+
+def _bf16_packs(st):
+    """every buffer of the bf16 staging the kernels read weights from, cloned"""
+    bf = st._compute[torch.bfloat16]
+    out = {k: bf[k].clone() for k in ("Wc", "Wt", "Wc_pad", "Wt_pad")}
+    for k in ("stems", "stems_t"):
+        out.update({"%s/%s" % (k, name): t.clone() for name, t in bf[k].items()})
+    return out
+
+
+@pytest.mark.parametrize("name,opt_name,case", [(C3, "adam", "all"), (C3, "adam", "frozen"), (C3, "adam", "frozen_overwritten"),
+                                                (C3, "sgd", "all"), (C3, "sgd", "frozen"), (C3, "sgd", "frozen_overwritten"),
+                                                (C5, "adam", "all")])
+def test_bf16_weight_copies_after_a_fused_step_equal_a_rebuild_from_the_parameters(name, opt_name, case, tiles):
+    """The step kernel writes the bf16 copy of the new parameters itself and `_finish` rebuilds only the packs derived from it
+    (compute_weights(skip_cast=True)): the next forward multiplies with what the kernel wrote.  After forward, backward and
+    step(), every bf16 staging buffer (Wc, Wt, the K-padded Wc_pad / Wt_pad -- the MobileNetV3 cfg has the most of those --, the
+    stems' packs) must be bit-identical to what a forced rebuild from P gives.
+    `frozen`: the prefix of test_freeze_layers_like_the_reference_harness is frozen; its moments stay zero and G is cleared.
+    `frozen_overwritten`: a frozen tensor is overwritten between backward and step (load_state_dict of a perturbed copy).  The
+    kernel skips frozen elements, so their bf16 copy is only right if somebody casts it again: before the fix in
+    dyk.optim._FusedBase (the cast is skipped only when the copy was current at the start of the step) this case failed on
+    MI355X, for both optimizers, with Wc stale (the packs derived from P were rebuilt, the plain bf16 copy was not)."""
+    from dyk.optim import FusedAdam, FusedSGD
+    assert tiles == "pinned"
+    m = _model(name, "bf16")
+    if case != "all":
+        for idx in range(224 + 1):
+            for p in m.module_list[idx].parameters():
+                p.requires_grad_(False)
+    opt = (FusedAdam if opt_name == "adam" else FusedSGD)(m, lr=1e-3, weight_decay=5e-4)
+    _backward(m, _batch(3))
+    st = m.engine.store
+    torch.cuda.synchronize()
+    before = _bf16_packs(st)
+    if case == "frozen_overwritten":
+        sd = {k: v.clone() for k, v in m.state_dict().items()}
+        frozen = [e.name for e in st.entries if not e.param.requires_grad]
+        assert frozen
+        for k in frozen:
+            sd[k] = sd[k] * 1.25 + 0.01
+        m.load_state_dict(sd)
+    opt.step()
+    torch.cuda.synchronize()
+    got = _bf16_packs(st)
+    st.compute_weights(torch.bfloat16, force=True)
+    torch.cuda.synchronize()
+    want = _bf16_packs(st)
+    assert list(got) == list(want)
+    stale = [k for k in got if not torch.equal(got[k].view(torch.uint8), want[k].view(torch.uint8))]
+    assert not stale, "bf16 staging buffers differ from a rebuild from P: %s" % stale
+    assert torch.equal(want["Wc"].view(torch.int16), st.P.bfloat16().view(torch.int16))
+    assert not torch.equal(got["Wc"].view(torch.int16), before["Wc"].view(torch.int16))       # the step did move the weights
+    if case != "all":
+        assert not bool(st.G.any())
+        for e in st.entries:
+            if not e.param.requires_grad:
+                assert not bool(st._view(opt._m, e).any()), e.name
+                assert opt._v is None or not bool(st._view(opt._v, e).any()), e.name
 
 
 def test_optimizer_state_dict_round_trip_and_format():

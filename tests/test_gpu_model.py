@@ -339,6 +339,45 @@ def test_torch_optimizer_and_fused_optimizer_agree():
     ref.step()
     ref.step()
     assert (st.P - P_sgd).abs().max().item() <= 2e-6
+    # Two steps from fresh state with ONE gradient move every element by +-lr whatever the betas are.  Three steps with a
+    # different gradient each (G scaled by a per-element factor in [-2, 2] before steps 2 and 3, identically for every optimizer)
+    # make the moment recurrences visible here too.  Bound: the trajectory bound of tests/test_gpu_optim.py -- the fused step
+    # may be at most OPTIM_K times as far from torch.optim in fp64 as torch.optim in fp32 is, after every step.
+    from helpers import OPTIM_K
+    gen = torch.Generator().manual_seed(5)
+    factors = [None] + [(torch.rand(G0.numel(), generator=gen) * 4 - 2).cuda() for _ in range(2)]
+
+    def three_steps(opt, P, G):
+        out = []
+        with torch.no_grad():
+            P.copy_(P0)
+            G.copy_(G0)
+        for f in factors:
+            if f is not None:
+                with torch.no_grad():
+                    G.mul_(f)
+            opt.step()
+            out.append(P.detach().double().clone())
+        return out
+
+    for kind in ("adam", "sgd"):
+        if kind == "adam":
+            kw = dict(lr=1e-3, betas=(0.937, 0.999), weight_decay=5e-4)
+            fused, make = FusedAdam(m, **kw), lambda ps: torch.optim.Adam(ps, foreach=False, **kw)
+        else:
+            kw = dict(lr=1e-2, momentum=0.937, weight_decay=5e-4)
+            fused, make = FusedSGD(m, **kw), lambda ps: torch.optim.SGD(ps, nesterov=True, foreach=False, **kw)
+        fused.zero_in_step = False
+        got = three_steps(fused, st.P, st.G)
+        r32 = three_steps(make(list(m.parameters())), st.P, st.G)
+        p64 = P0.double().clone().requires_grad_(True)
+        p64.grad = torch.zeros_like(p64)
+        r64 = three_steps(make([p64]), p64, p64.grad)
+        assert not torch.equal(got[2], got[1])
+        for t in range(3):
+            e_k, e_t = float((got[t] - r64[t]).abs().max()), float((r32[t] - r64[t]).abs().max())
+            print("%s step %d: E_k %.3e E_t %.3e ratio %.2f" % (kind, t + 1, e_k, e_t, e_k / e_t))
+            assert e_k <= OPTIM_K[kind] * e_t, (kind, t, e_k, e_t)
 
 
 def test_bf16_autocast_train_step_statistics():
