@@ -426,15 +426,21 @@ inline int ew_grid2d(int CV, long npix, int* gx, int* gy) {
     case DYK_ACT_HSWISH: hipLaunchKernelGGL((KERNEL<T, DYK_ACT_HSWISH>), __VA_ARGS__); break;                      \
     default: return DYK_ERR_ARG;                                                                                   \
     }
+// DYK_BN_LAUNCH: training passes (bf16 | f32); DYK_BN_LAUNCH_F: the forward pass an inference plan issues (+ f16)
+#define DYK_BN_LAUNCH_F(KERNEL, ...)                                      \
+    if (d->dtype == DYK_F16) { DYK_BN_LAUNCH_ACT(KERNEL, f16_t, __VA_ARGS__) } \
+    else if (d->dtype == DYK_BF16) { DYK_BN_LAUNCH_ACT(KERNEL, bf16_t, __VA_ARGS__) } \
+    else { DYK_BN_LAUNCH_ACT(KERNEL, float, __VA_ARGS__) }
 #define DYK_BN_LAUNCH(KERNEL, ...)                                        \
+    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;                  \
     if (d->dtype == DYK_BF16) { DYK_BN_LAUNCH_ACT(KERNEL, bf16_t, __VA_ARGS__) } \
     else { DYK_BN_LAUNCH_ACT(KERNEL, float, __VA_ARGS__) }
 
 inline int ew_check(const DykEwDesc* d, bool need_b) {
     if (!d || !d->a || !d->out || d->npix <= 0 || d->C <= 0) return DYK_ERR_ARG;
     if (need_b && !d->b) return DYK_ERR_ARG;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
-    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32) return DYK_ERR_ARG;
+    const int epv = d->dtype == DYK_F32 ? 4 : 8;
+    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32 && d->dtype != DYK_F16) return DYK_ERR_ARG;
     if (d->C % epv || d->lda % epv || d->ldo % epv || (d->b && d->ldb % epv)) return DYK_ERR_ARG;
     return DYK_OK;
 }
@@ -464,13 +470,13 @@ extern "C" int dyk_bn_fold(const float* gamma, const float* beta, const float* r
 extern "C" int dyk_bn_act_fwd(const DykEwDesc* d, void* stream) {
     const int rc = ew_check(d, false);
     if (rc) return rc;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
+    const int epv = d->dtype == DYK_F32 ? 4 : 8;
     int gx, gy;
     const int CVB = ew_grid2d(d->C / epv, d->npix, &gx, &gy);
     DykEwPair pr;
     const int nz = dyk_fill_ew_pair(pr, d);
     if (!nz) return DYK_ERR_ARG;
-    DYK_BN_LAUNCH(bn_act_fwd_kernel, dim3(gx, gy, nz), dim3(256), 0, (hipStream_t)stream, pr, CVB)
+    DYK_BN_LAUNCH_F(bn_act_fwd_kernel, dim3(gx, gy, nz), dim3(256), 0, (hipStream_t)stream, pr, CVB)
     DYK_LAUNCH_CHECK();
     return DYK_OK;
 }
@@ -480,7 +486,7 @@ extern "C" int dyk_bn_finalize_act_fwd(const DykBnFinalizeDesc* f, const DykEwDe
     const int rc = ew_check(d, false);
     if (rc) return rc;
     if (d->C != f->C) return DYK_ERR_ARG;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
+    const int epv = d->dtype == DYK_F32 ? 4 : 8;
     int gx, gy;
     const int CVB = ew_grid2d(d->C / epv, d->npix, &gx, &gy);
     DykEwPair pr;
@@ -494,8 +500,9 @@ extern "C" int dyk_bn_finalize_act_fwd(const DykBnFinalizeDesc* f, const DykEwDe
 
 extern "C" int dyk_bn_act_bwd_reduce(const DykEwDesc* d, void* stream) {
     if (!d || !d->a || !d->b || !d->red || !d->p0 || !d->p1 || !d->p2 || !d->p3) return DYK_ERR_ARG;
+    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;       // (the inference type has no backward forms)
     if (d->npix <= 0 || d->C <= 0 || (d->dtype != DYK_BF16 && d->dtype != DYK_F32)) return DYK_ERR_ARG;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
+    const int epv = d->dtype == DYK_F32 ? 4 : 8;
     if (d->C % epv || d->lda % epv || d->ldb % epv) return DYK_ERR_ARG;
     const int CV = d->C / epv;
     int CVB = 1;
@@ -527,7 +534,7 @@ extern "C" int dyk_bn_act_bwd_apply(const DykEwDesc* d, void* stream) {
     if (rc) return rc;
     if (d->flags & DYK_EW_SKIP) return DYK_OK;          // done inside the consumer (DykStemDesc.bn_fused)
     if (!d->red || !d->p0 || !d->p1 || !d->p2 || !d->p3) return DYK_ERR_ARG;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
+    const int epv = d->dtype == DYK_F32 ? 4 : 8;
     int gx, gy;
     const int CVB = ew_grid2d(d->C / epv, d->npix, &gx, &gy);
     DykEwPair pr;

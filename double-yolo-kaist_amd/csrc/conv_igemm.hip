@@ -22,6 +22,8 @@ static int conv_validate(const DykConvDesc* d) {
         if (d->cls_first[c] < 0 || d->cls_ntaps[c] < 0 || d->cls_first[c] + d->cls_ntaps[c] > d->ntaps || d->cls_ooy[c] < 0 ||
             d->cls_ooy[c] >= d->osy || d->cls_oox[c] < 0 || d->cls_oox[c] >= d->osx)
             return DYK_ERR_ARG;
+    // f16 is the inference type: forward epilogues only (no statistics, no fused BatchNorm forms)
+    if (d->dtype == DYK_F16 && (d->flags & (DYK_EPI_STATS | DYK_EPI_BNFWD | DYK_EPI_BNBWD | DYK_EPI_ADDEND))) return DYK_ERR_UNSUPPORTED;
     if ((d->flags & DYK_EPI_STATS) && !d->stats) return DYK_ERR_ARG;
     if ((d->flags & DYK_EPI_RESIDUAL) && !d->res) return DYK_ERR_ARG;
     if ((d->flags & DYK_EPI_ADDEND) && (!(d->flags & DYK_EPI_BNBWD) || ((uintptr_t)d->add % 16))) return DYK_ERR_ARG;     // (add == NULL: zero addend)
@@ -38,7 +40,7 @@ static int conv_validate(const DykConvDesc* d) {
     if (d->flags & DYK_EPI_BNBWD) {
         if (d->flags & (DYK_EPI_AFFINE | DYK_EPI_RESIDUAL | DYK_EPI_STATS | DYK_EPI_ACCUM | DYK_EPI_OUT_F32)) return DYK_ERR_ARG;
         if (!d->res || !d->stats || !d->scale || !d->shift || !d->aux0 || !d->aux1) return DYK_ERR_ARG;
-        const int es = d->dtype == DYK_BF16 ? 2 : 4;
+        const int es = d->dtype == DYK_F32 ? 4 : 2;
         // needs the staged (vector) epilogue: 16-byte aligned rows of y and res, whole 16-byte channel chunks
         if (d->Cout % (16 / es) || ((size_t)d->ldy * es) % 16 || ((size_t)d->ldr * es) % 16 || ((uintptr_t)d->y % 16) ||
             ((uintptr_t)d->res % 16))
@@ -51,8 +53,8 @@ static int conv_validate(const DykConvDesc* d) {
             return DYK_ERR_ARG;
         if (d->twin || d->ncls > 1 || (d->flags & DYK_EPI_BNFWD)) return DYK_ERR_ARG;
     }
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
-    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32) return DYK_ERR_ARG;
+    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32 && d->dtype != DYK_F16) return DYK_ERR_ARG;
+    const int epv = d->dtype == DYK_F32 ? 4 : 8;
     if (d->ldx % epv || ((uintptr_t)d->x % 16) || ((uintptr_t)d->w % 16)) return DYK_ERR_ARG;
     // 32-bit element offsets inside the kernel
     if ((long)d->B * d->Hi * d->Wi * d->ldx >= (1L << 31)) return DYK_ERR_ARG;
@@ -71,7 +73,7 @@ extern "C" int dyk_conv_igemm(const DykConvDesc* d, void* stream) {
         if (memcmp((const char*)d + lo, (const char*)d->twin + lo, hi - lo) != 0) return DYK_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-    const int tile = d->dtype == DYK_BF16 ? (d->tune >> 12) & 0xf : 0;      // 80 / 160 pixel tiles are built for bf16 only
+    const int tile = d->dtype != DYK_F32 ? (d->tune >> 12) & 0xf : 0;      // 80 / 160 pixel tiles are built for the 16-bit types only
     if (d->flags & DYK_EPI_BNFWD) {        // generic tiles only (the halo / K-grouped kernels do not carry this epilogue)
         if (tile == 1 || tile == 3) return dyk_conv_launch_n80(d, s);
         if (tile == 2 || tile == 4) return dyk_conv_launch_n160(d, s);
@@ -83,7 +85,7 @@ extern "C" int dyk_conv_igemm(const DykConvDesc* d, void* stream) {
         return dyk_conv_launch_n160(d, s);
     }
     if (tile == 6) {                       // resident-weight 3x3 data gradient into 32-channel tensors (conv_sc.hip)
-        const int rc = d->splitk > 1 ? DYK_ERR_UNSUPPORTED : dyk_conv_launch_sc(d, s);
+        const int rc = (d->splitk > 1 || d->dtype != DYK_BF16) ? DYK_ERR_UNSUPPORTED : dyk_conv_launch_sc(d, s);
         if (rc != DYK_ERR_UNSUPPORTED || ((d->tune >> 23) & 1)) return rc;       // (bit 23, analysis: no fallback)
         return dyk_conv_launch_n128(d, s);
     }
@@ -94,11 +96,11 @@ extern "C" int dyk_conv_igemm(const DykConvDesc* d, void* stream) {
     }
     if (((d->tune >> 28) & 7) == 1) {      // K-grouped workgroups (conv_igemm_kg.hip); generic tiles where they do not apply
         const int rc = dyk_conv_launch_kg(d, s);
-        if (rc != DYK_ERR_UNSUPPORTED) return rc;
+        if (rc != DYK_ERR_UNSUPPORTED || ((d->tune >> 23) & 1)) return rc;       // (bit 23, analysis: no fallback)
     }
     if (tile == 3 || tile == 4) {          // 3x3 halo kernel; falls back to the generic tiles when the problem does not fit it
         const int rc = dyk_conv_launch_halo(d, s, tile == 3 ? 4 : 8);
-        if (rc != DYK_ERR_UNSUPPORTED) return rc;
+        if (rc != DYK_ERR_UNSUPPORTED || ((d->tune >> 23) & 1)) return rc;       // (bit 23, analysis: no fallback)
         return tile == 3 ? dyk_conv_launch_n80(d, s) : dyk_conv_launch_n160(d, s);
     }
     if (tile == 1) return dyk_conv_launch_n80(d, s);
@@ -111,7 +113,7 @@ extern "C" int dyk_conv_bnfwd_max_grid(void) { return 256; }
 // workgroups of the generic-tile launch of `d` (the tile selection of dispatch_conv_bn; halo / K-grouped launches differ)
 extern "C" int dyk_conv_grid(const DykConvDesc* d) {
     if (!d || d->B <= 0 || d->Hg <= 0 || d->Wg <= 0 || d->Cout <= 0) return DYK_ERR_ARG;
-    const int tile = d->dtype == DYK_BF16 ? (d->tune >> 12) & 0xf : 0;
+    const int tile = d->dtype != DYK_F32 ? (d->tune >> 12) & 0xf : 0;
     const int bn = (tile == 1 || tile == 3) ? 80 : ((tile == 2 || tile == 4) ? 160 : 128);
     int bm = d->Cout > 64 ? 128 : (d->Cout > 32 ? 64 : 32);
     const int bm_code = (d->tune >> 24) & 0xf;
@@ -129,7 +131,7 @@ extern "C" int64_t dyk_conv_splitk_ws_bytes(const DykConvDesc* d, int32_t* tiles
     if (!d || d->B <= 0 || d->Hg <= 0 || d->Wg <= 0 || d->Cout <= 0) return DYK_ERR_ARG;
     if (d->splitk <= 1) return 0;
     const long n = (long)d->B * d->Hg * d->Wg;
-    const int tile = d->dtype == DYK_BF16 ? (d->tune >> 12) & 0xf : 0;
+    const int tile = d->dtype != DYK_F32 ? (d->tune >> 12) & 0xf : 0;
     int64_t bytes = 0;
     int32_t nt = 0;
     auto cover = [&](int bm, int bn) {

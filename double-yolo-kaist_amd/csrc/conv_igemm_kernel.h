@@ -7,7 +7,7 @@
 // Block = 256 threads = 4 waves, tile BM x BN (BN = 80 | 128 | 160 pixels), K step = BKB bytes of channels
 // (64 or 128 B per row).  Global -> LDS by LDS-DMA (XOR-swizzled 16-byte slots, zero fill for
 // padding taps / ragged tiles from a zero page), 2- or 3-stage ring, one barrier per K step.
-// MFMA: v_mfma_f32_16x16x32_bf16 (bf16) or 4 x v_mfma_f32_16x16x4_f32 (f32) per 16-byte
+// MFMA: v_mfma_f32_16x16x32_bf16 (bf16), v_mfma_f32_16x16x32_f16 (f16) or 4 x v_mfma_f32_16x16x4_f32 (f32) per 16-byte
 // fragment pair; both operands are read from LDS with the same (row = lane&15,
 // slot = lane>>4) pattern so the K permutation inside a fragment cancels.
 // D layout: acc[r] = D[m = (lane>>4)*4 + r][n = lane&15]  -> four consecutive output
@@ -70,6 +70,12 @@ template <> struct Mma<bf16_t> {
     static __device__ inline void run(f32x4_t& acc, const uint4& a, const uint4& b) {
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
                                                       __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
+    }
+};
+template <> struct Mma<f16_t> {                           // same shape, rate and operand layout as the bf16 form
+    static __device__ inline void run(f32x4_t& acc, const uint4& a, const uint4& b) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a),
+                                                     __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
     }
 };
 template <> struct Mma<float> {
@@ -222,6 +228,7 @@ __device__ __forceinline__ void conv_epilogue(const DykConvDesc& desc, f32x4_t (
     const bool has_res = (flags & DYK_EPI_RESIDUAL) && EPIK != 3;     // (EPIK 3 adds the residual in its own second pass)
     const bool accum = flags & DYK_EPI_ACCUM;
     const bool out_f32 = (flags & DYK_EPI_OUT_F32) || sizeof(T) == 4;
+    using H16 = typename Half16<T>::type;                 // 16-bit storage type of the output (bf16 | f16)
 
     if (flags & EPI_INTERNAL_VEC) {
         // ---- staged, coalesced store: accumulators -> LDS tile [pixel][channel] -> 16-byte global stores
@@ -269,8 +276,8 @@ __device__ __forceinline__ void conv_epilogue(const DykConvDesc& desc, f32x4_t (
                         *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
                     } else {
                         uint2 pk;
-                        pk.x = f32x2_to_bf16x2(v[0], v[1]);
-                        pk.y = f32x2_to_bf16x2(v[2], v[3]);
+                        pk.x = f32x2_to_h2<T>(v[0], v[1]);
+                        pk.y = f32x2_to_h2<T>(v[2], v[3]);
                         *(uint2*)dst = pk;
                     }
                 }
@@ -305,34 +312,34 @@ __device__ __forceinline__ void conv_epilogue(const DykConvDesc& desc, f32x4_t (
                         for (int j = 0; j < 4; ++j) if (mc + j < a.Cout) yp[j] = f[j];
                     }
                 } else {
-                    bf16_t* yp = (bf16_t*)a.y + (long)po + mc;
+                    H16* yp = (H16*)a.y + (long)po + mc;
                     if (whole && !has_res && !accum) {
                         *(uint4*)yp = val;
                     } else if (whole) {
                         float f[8];
-                        vec_unpack<bf16_t>(val, f);
+                        vec_unpack<H16>(val, f);
                         if (has_res) {
                             float g[8];
-                            vec_unpack<bf16_t>(*(const uint4*)((const bf16_t*)a.res + (long)t_res[row] + mc), g);
+                            vec_unpack<H16>(*(const uint4*)((const H16*)a.res + (long)t_res[row] + mc), g);
 #pragma unroll
                             for (int j = 0; j < 8; ++j) f[j] += g[j];
                         }
                         if (accum) {
                             float g[8];
-                            vec_unpack<bf16_t>(*(const uint4*)yp, g);
+                            vec_unpack<H16>(*(const uint4*)yp, g);
 #pragma unroll
                             for (int j = 0; j < 8; ++j) f[j] += g[j];
                         }
-                        *(uint4*)yp = vec_pack<bf16_t>(f);
+                        *(uint4*)yp = vec_pack<H16>(f);
                     } else {
                         float f[8];
-                        vec_unpack<bf16_t>(val, f);
+                        vec_unpack<H16>(val, f);
                         for (int j = 0; j < 8; ++j) {
                             if (mc + j >= a.Cout) break;
                             float u = f[j];
-                            if (has_res) u += bf16_to_f32(((const bf16_t*)a.res + (long)t_res[row] + mc)[j]);
-                            if (accum) u += bf16_to_f32(yp[j]);
-                            yp[j] = f32_to_bf16(u);
+                            if (has_res) u += ElemTraits<H16>::to_f32(((const H16*)a.res + (long)t_res[row] + mc)[j]);
+                            if (accum) u += ElemTraits<H16>::to_f32(yp[j]);
+                            yp[j] = ElemTraits<H16>::from_f32(u);
                         }
                     }
                 }
@@ -859,10 +866,10 @@ __device__ __forceinline__ void conv_epilogue(const DykConvDesc& desc, f32x4_t (
                 for (int r = 0; r < 4; ++r)
                     if (m + r < a.Cout) yp[r] = accum ? yp[r] + v[r] : v[r];
             } else {
-                bf16_t* yp = (bf16_t*)a.y + (long)po + m;
+                H16* yp = (H16*)a.y + (long)po + m;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (m + r < a.Cout) yp[r] = f32_to_bf16(accum ? bf16_to_f32(yp[r]) + v[r] : v[r]);
+                    if (m + r < a.Cout) yp[r] = ElemTraits<H16>::from_f32(accum ? ElemTraits<H16>::to_f32(yp[r]) + v[r] : v[r]);
             }
         }
     }
@@ -1507,7 +1514,7 @@ inline bool conv_vec_ok(const DykConvDesc* d, int eso, size_t elem) {
 }
 
 inline bool conv_halo_eligible(const DykConvDesc* d, int TH) {
-    if (d->dtype != DYK_BF16 || d->ntaps != 9 || d->splitk > 1) return false;      // (split-K: generic / large-tile kernels only)
+    if ((d->dtype != DYK_BF16 && d->dtype != DYK_F16) || d->ntaps != 9 || d->splitk > 1) return false;      // (split-K: generic / large-tile kernels only)
     if (d->isy != 1 || d->isx != 1 || d->osy != 1 || d->osx != 1 || d->ooy != 0 || d->oox != 0) return false;
     if (d->Hg != d->Hi || d->Wg != d->Wi || d->Ho != d->Hi || d->Wo != d->Wi) return false;
     if (d->Wi % 20 || d->Hi % TH) return false;

@@ -4,7 +4,9 @@
 
 int dyk_conv_launch_n160b(const DykConvDesc* d, hipStream_t s);
 int dyk_conv_launch_n160n(const DykConvDesc* d, hipStream_t s);
+int dyk_conv_launch_n160h(const DykConvDesc* d, hipStream_t s);
 int dyk_conv_launch_n160(const DykConvDesc* d, hipStream_t s) {
+    if (d->dtype == DYK_F16) return dyk_conv_launch_n160h(d, s);
     if (d->flags & DYK_EPI_BNFWD) return dyk_conv_launch_n160n(d, s);
     if (d->flags & DYK_EPI_BNBWD) return dyk_conv_launch_n160b(d, s);
     if (d->dtype == DYK_BF16) return dispatch_conv_bn<bf16_t, 160>(d, s);

@@ -1,0 +1,7 @@
+// 160-pixel tile, f16 (IEEE half, inference plans): forward epilogues only
+#include "conv_igemm_kernel.h"
+
+int dyk_conv_launch_n160h(const DykConvDesc* d, hipStream_t s) {
+    if (d->dtype != DYK_F16) return DYK_ERR_UNSUPPORTED;
+    return dispatch_conv_bn<f16_t, 160>(d, s);
+}

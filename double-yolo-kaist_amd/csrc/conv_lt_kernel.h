@@ -29,7 +29,7 @@
 
 namespace {
 
-constexpr int LT_ROWB = 64;                 // bytes per LDS row = 32 bf16 channels per K step
+constexpr int LT_ROWB = 64;                 // bytes per LDS row = 32 channels (bf16 | f16) per K step
 // LAG = steps whose DMA may still be in flight when a step ends (counted vmcnt).  Weight tiles are issued LAG + 2 steps ahead
 // into a ring of LAG + 3 stages; the halo of the next chunk is issued during tap steps 0 .. 7 - LAG of the current one.
 constexpr int LT_LAG = 2;
@@ -46,11 +46,11 @@ inline LtGeom lt_geom(int TH, int TW) {
 template <int BM, int BN> constexpr int lt_table_bytes() { return BN * 8 + 1024 + 8 * 2 * BM * 4; }
 template <int BM, int BN> constexpr int lt_rings_off() { return (lt_table_bytes<BM, BN>() + 1023) & ~1023; }
 
-template <int WMn, int WNn, int KG, int EPIK>
+template <int WMn, int WNn, int KG, int EPIK, typename T = bf16_t>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void conv_lt_kernel(const ConvArgs args, const int TH, const int TW) {
     static_assert(WMn * WNn * KG == 8, "eight waves");
-    using T = bf16_t;
+    static_assert(sizeof(T) == 2, "16-bit elements (bf16 | f16)");
     constexpr int BM = 64 * WMn, BN = 80 * WNn;
     constexpr int GW = WMn * WNn;                  // waves per K-group
     constexpr int GT = 64 * GW;                    // threads per K-group (= the threads that run the epilogue)
@@ -327,7 +327,7 @@ inline bool lt_pick_patch(int H, int W, int BN, int GW, int code, LtGeom& g) {
 }
 
 inline bool conv_lt_eligible(const DykConvDesc* d) {
-    if (d->dtype != DYK_BF16 || d->ntaps != 9 || d->ncls > 1 || d->twin) return false;
+    if ((d->dtype != DYK_BF16 && d->dtype != DYK_F16) || d->ntaps != 9 || d->ncls > 1 || d->twin) return false;
     if (d->isy != 1 || d->isx != 1 || d->osy != 1 || d->osx != 1 || d->ooy != 0 || d->oox != 0) return false;
     if (d->Hg != d->Hi || d->Wg != d->Wi || d->Ho != d->Hi || d->Wo != d->Wi) return false;
     if (d->Cin % 32 || d->Cout % 8) return false;
@@ -337,7 +337,7 @@ inline bool conv_lt_eligible(const DykConvDesc* d) {
     return true;
 }
 
-template <int WMn, int WNn, int KG, int EPIK>
+template <int WMn, int WNn, int KG, int EPIK, typename T = bf16_t>
 int launch_conv_lt(const DykConvDesc* d, hipStream_t stream) {
     constexpr int BM = 64 * WMn, BN = 80 * WNn, GW = WMn * WNn;
     if (!conv_lt_eligible(d)) return DYK_ERR_UNSUPPORTED;
@@ -357,7 +357,7 @@ int launch_conv_lt(const DykConvDesc* d, hipStream_t stream) {
     if (park > lds) lds = park;
     if (lds > 160 * 1024) return DYK_ERR_UNSUPPORTED;
     static DykDeviceOnce attr_set;   // (the attribute is per DEVICE: one flag per device id)
-    auto kfn = conv_lt_kernel<WMn, WNn, KG, EPIK>;
+    auto kfn = conv_lt_kernel<WMn, WNn, KG, EPIK, T>;
     if (attr_set.first()) {
         DYK_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
@@ -373,12 +373,12 @@ int launch_conv_lt(const DykConvDesc* d, hipStream_t stream) {
 
 // tune word of the large-tile kernels: pixel-tile code 5 (bits 12..15), shape in bits 8..11 (1 = 128 x 320, 2 = 256 x 160,
 // 3 = 128 x 160 with two K-groups), patch width code in bits 24..27 (0 = fewest halo rows, k: TW = 10 << k)
-template <int EPIK>
+template <int EPIK, typename T = bf16_t>
 int dispatch_conv_lt(const DykConvDesc* d, hipStream_t stream) {
     switch ((d->tune >> 8) & 0xf) {
-    case 1: return launch_conv_lt<2, 4, 1, EPIK>(d, stream);
-    case 2: return launch_conv_lt<4, 2, 1, EPIK>(d, stream);
-    case 3: return launch_conv_lt<2, 2, 2, EPIK>(d, stream);
+    case 1: return launch_conv_lt<2, 4, 1, EPIK, T>(d, stream);
+    case 2: return launch_conv_lt<4, 2, 1, EPIK, T>(d, stream);
+    case 3: return launch_conv_lt<2, 2, 2, EPIK, T>(d, stream);
     default: return DYK_ERR_UNSUPPORTED;
     }
 }

@@ -84,10 +84,10 @@ template <int BM, int WM, int BN, int BKB> constexpr size_t pw_lds_bytes(int kc,
 
 // EPI: 0 = plain store, 1 = store + BatchNorm statistics (DYK_EPI_STATS), 2 = fused BatchNorm-backward reduce (DYK_EPI_BNBWD),
 //      3 = the same in residual-chain form (| DYK_EPI_ADDEND).  ACTB: activation of the BatchNorm being differentiated (-1: runtime)
-template <int BM, int WM, int BN, int BKB, int EPI, int ACTB>
+template <int BM, int WM, int BN, int BKB, int EPI, int ACTB, typename T = bf16_t>
 __global__ __launch_bounds__(256) void conv_pw_kernel(const PwArgs g) {
     using C = PwCfg<BM, WM, BN, BKB>;
-    using T = bf16_t;
+    static_assert(sizeof(T) == 2 && (EPI == 0 || !__is_same(T, f16_t)), "16-bit elements; f16: plain store only");
     constexpr int WN = C::WN, WTM = C::WTM, WTN = C::WTN, MI = C::MI, NI = C::NI, KK = C::KK, BK = C::BK;
     constexpr int SPR = C::SPR, RPI = C::RPI, IPCX = C::IPCX, IPCW = C::IPCW;
     constexpr int RB = C::RB, CPR = C::CPR, RPIU = C::RPIU, NDU = C::NDU, NSTW = C::NSTW;
@@ -239,8 +239,8 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(const PwArgs g) {
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) {
                     uint2 pk;
-                    pk.x = f32x2_to_bf16x2(acc[mi][ni][0], acc[mi][ni][1]);
-                    pk.y = f32x2_to_bf16x2(acc[mi][ni][2], acc[mi][ni][3]);
+                    pk.x = f32x2_to_h2<T>(acc[mi][ni][0], acc[mi][ni][1]);
+                    pk.y = f32x2_to_h2<T>(acc[mi][ni][2], acc[mi][ni][3]);
                     *(uint2*)(sEw + (ni * 16 + frow) * RS + (mi * 16 + mlane) * 2) = pk;
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -348,7 +348,8 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(const PwArgs g) {
 }
 
 inline bool conv_pw_eligible(const DykConvDesc* d) {
-    if (d->dtype != DYK_BF16 || d->ntaps != 1 || d->tdy[0] || d->tdx[0] || d->ncls > 1 || d->twin || d->splitk > 1) return false;
+    // (f16, the inference type: the plain store only)
+    if ((d->dtype != DYK_BF16 && !(d->dtype == DYK_F16 && d->flags == 0)) || d->ntaps != 1 || d->tdy[0] || d->tdx[0] || d->ncls > 1 || d->twin || d->splitk > 1) return false;
     if (d->isy != 1 || d->isx != 1 || d->osy != 1 || d->osx != 1 || d->ooy != 0 || d->oox != 0) return false;
     if (d->Hg != d->Hi || d->Wg != d->Wi || d->Ho != d->Hi || d->Wo != d->Wi) return false;
     const int f = d->flags;
@@ -363,7 +364,7 @@ inline bool conv_pw_eligible(const DykConvDesc* d) {
     return true;
 }
 
-template <int BM, int WM, int BN, int BKB, int EPI, int ACTB>
+template <int BM, int WM, int BN, int BKB, int EPI, int ACTB, typename T = bf16_t>
 int launch_conv_pw(const DykConvDesc* d, hipStream_t stream) {
     using C = PwCfg<BM, WM, BN, BKB>;
     const int kc = d->Cin * 2 / BKB;
@@ -384,7 +385,7 @@ int launch_conv_pw(const DykConvDesc* d, hipStream_t stream) {
     const size_t lds = pw_lds_bytes<BM, WM, BN, BKB>(kc, nxs, EPI);
     if (lds > 160 * 1024 || young_of(nxs) > 60) return DYK_ERR_UNSUPPORTED;
     static DykDeviceOnce attr_set;   // (the attribute is per DEVICE: one flag per device id)
-    auto kfn = conv_pw_kernel<BM, WM, BN, BKB, EPI, ACTB>;
+    auto kfn = conv_pw_kernel<BM, WM, BN, BKB, EPI, ACTB, T>;
     if (attr_set.first()) {
         DYK_HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
@@ -408,26 +409,26 @@ int launch_conv_pw(const DykConvDesc* d, hipStream_t stream) {
 
 // tune word of the pointwise kernels: pixel-tile code 7 (bits 12..15), ring stages in bits 8..11 (0 = 3), bit 24 = 128-pixel tiles
 // (channel tiles <= 64 rows only), bit 25 = 32-pixel tiles (128-row channel tiles only)
-template <int EPI, int ACTB>
+template <int EPI, int ACTB, typename T = bf16_t>
 int dispatch_conv_pw(const DykConvDesc* d, hipStream_t s) {
     const bool bn128 = (d->tune >> 24) & 1;
     const bool k128 = (d->Cin % 64) == 0;
     if (d->Cout <= 32) {
-        if (bn128) return k128 ? launch_conv_pw<32, 1, 128, 128, EPI, ACTB>(d, s) : launch_conv_pw<32, 1, 128, 64, EPI, ACTB>(d, s);
-        return k128 ? launch_conv_pw<32, 1, 64, 128, EPI, ACTB>(d, s) : launch_conv_pw<32, 1, 64, 64, EPI, ACTB>(d, s);
+        if (bn128) return k128 ? launch_conv_pw<32, 1, 128, 128, EPI, ACTB, T>(d, s) : launch_conv_pw<32, 1, 128, 64, EPI, ACTB, T>(d, s);
+        return k128 ? launch_conv_pw<32, 1, 64, 128, EPI, ACTB, T>(d, s) : launch_conv_pw<32, 1, 64, 64, EPI, ACTB, T>(d, s);
     }
     if (d->Cout <= 64) {
-        if (bn128) return k128 ? launch_conv_pw<64, 1, 128, 128, EPI, ACTB>(d, s) : launch_conv_pw<64, 1, 128, 64, EPI, ACTB>(d, s);
-        return k128 ? launch_conv_pw<64, 1, 64, 128, EPI, ACTB>(d, s) : launch_conv_pw<64, 1, 64, 64, EPI, ACTB>(d, s);
+        if (bn128) return k128 ? launch_conv_pw<64, 1, 128, 128, EPI, ACTB, T>(d, s) : launch_conv_pw<64, 1, 128, 64, EPI, ACTB, T>(d, s);
+        return k128 ? launch_conv_pw<64, 1, 64, 128, EPI, ACTB, T>(d, s) : launch_conv_pw<64, 1, 64, 64, EPI, ACTB, T>(d, s);
     }
     if (bn128) return DYK_ERR_UNSUPPORTED;
     if ((d->tune >> 25) & 1)               // 32-pixel tiles: smaller ring stages and staging, two workgroups per CU at K = 128
-        return k128 ? launch_conv_pw<128, 2, 32, 128, EPI, ACTB>(d, s) : DYK_ERR_UNSUPPORTED;
+        return k128 ? launch_conv_pw<128, 2, 32, 128, EPI, ACTB, T>(d, s) : DYK_ERR_UNSUPPORTED;
     // 128-row channel tiles (two for 136..256 output channels: the activation tile is then read by two workgroups, through L2);
     // 32-pixel tiles where K = 256 and the epilogue operands of the BatchNorm-backward forms do not fit beside 64-pixel tiles
-    const int rc = k128 ? launch_conv_pw<128, 2, 64, 128, EPI, ACTB>(d, s) : launch_conv_pw<128, 2, 64, 64, EPI, ACTB>(d, s);
+    const int rc = k128 ? launch_conv_pw<128, 2, 64, 128, EPI, ACTB, T>(d, s) : launch_conv_pw<128, 2, 64, 64, EPI, ACTB, T>(d, s);
     if (rc != DYK_ERR_UNSUPPORTED) return rc;
-    if constexpr (EPI >= 2) return k128 ? launch_conv_pw<128, 2, 32, 128, EPI, ACTB>(d, s) : DYK_ERR_UNSUPPORTED;
+    if constexpr (EPI >= 2) return k128 ? launch_conv_pw<128, 2, 32, 128, EPI, ACTB, T>(d, s) : DYK_ERR_UNSUPPORTED;
     return rc;
 }
 

@@ -245,10 +245,10 @@ __global__ __launch_bounds__(256) void dwconv_strip_kernel(DykDwDesc d, int CVB)
 // dependent batches per strip (one round trip per kernel row): 1.1-1.9 TB/s on the MobileNetV3 layers, latency-bound.
 // Thread = (channel vector ct, strip of XT = 4 pixels, tile row); tile [rows][cols][S = CT|1] 16-byte slots (odd slot
 // stride: <= 2-way bank conflicts, irrelevant next to the VALU work); weights [K*K][CT*8] fp32 behind the tile.
-template <int K, bool GRAD>
+template <int K, bool GRAD, typename T = bf16_t>
 __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, int groups, unsigned m_ct, int tiles_x,
                                                           int tiles_y) {
-    using T = bf16_t;
+    static_assert(sizeof(T) == 2, "16-bit elements (bf16 | f16)");
     constexpr int EPV = 8, TW = 16, XT = 4, SPR = TW / XT, NS = XT + K - 1, IC = TW + K - 1;
     constexpr int NLD = K == 5 ? 8 : 6;                       // staging loads per thread (host checks the tile fits)
     extern __shared__ uint4 smem[];
@@ -472,7 +472,7 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, i
     }
 }
 
-template <int K, bool GRAD>
+template <int K, bool GRAD, typename T = bf16_t>
 int launch_dw_tile(const DykDwDesc* d, hipStream_t stream) {
     constexpr int TW = 16, IC = TW + K - 1, NLD = K == 5 ? 8 : 6;
     const int CV = d->C / 8;
@@ -486,7 +486,7 @@ int launch_dw_tile(const DykDwDesc* d, hipStream_t stream) {
     const unsigned m_ct = (unsigned)(0xFFFFFFFFu / (unsigned)CT) + 1u;   // idx / CT == umulhi(idx, m_ct) for idx < 2^32 / CT
     const long nblk = (long)groups * tiles_x * tiles_y * d->B;
     if (nblk >= (1L << 31) || lds > 64 * 1024) return DYK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((dwconv_tile_kernel<K, GRAD>), dim3((unsigned)nblk), dim3(256), lds, stream, *d, CT, groups,
+    hipLaunchKernelGGL((dwconv_tile_kernel<K, GRAD, T>), dim3((unsigned)nblk), dim3(256), lds, stream, *d, CT, groups,
                        m_ct, tiles_x, tiles_y);
     return DYK_OK;
 }
@@ -1003,8 +1003,8 @@ inline int launch_dw_wgrad_tile(const DykDwDesc* d, const DwWgTile& c, hipStream
 
 int check_dw(const DykDwDesc* d) {
     if (!d || !d->x || !d->y || d->B <= 0 || d->C <= 0 || d->k <= 0 || d->k > 7 || d->stride <= 0) return DYK_ERR_ARG;
-    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32) return DYK_ERR_ARG;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
+    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32 && d->dtype != DYK_F16) return DYK_ERR_ARG;
+    const int epv = d->dtype == DYK_F32 ? 4 : 8;
     if (d->C % epv || d->ldx % epv || d->ldy % epv) return DYK_ERR_ARG;
     if (d->Hi <= 0 || d->Wi <= 0 || d->Ho <= 0 || d->Wo <= 0) return DYK_ERR_ARG;
     return DYK_OK;
@@ -1029,9 +1029,22 @@ extern "C" int dyk_dwconv_fwd(const DykDwDesc* d, void* stream) {
     const int rc = check_dw(d);
     if (rc) return rc;
     if (!d->w) return DYK_ERR_ARG;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
+    const int epv = d->dtype == DYK_F32 ? 4 : 8;
     int gx, gy;
     const int CVB = grid2d(d->C / epv, (long)d->B * d->Ho, &gx, &gy, 4096);
+    if (d->dtype == DYK_F16) {
+        // the inference type: the same kernel choice as bf16, no BatchNorm statistics, no normalise-on-load (train-mode forms)
+        if (d->stats || d->pre) return DYK_ERR_UNSUPPORTED;
+        if (d->stride == 1 && (d->k == 3 || d->k == 5) && dw_tile_on()) {
+            const int rt = d->k == 3 ? launch_dw_tile<3, false, f16_t>(d, (hipStream_t)stream) : launch_dw_tile<5, false, f16_t>(d, (hipStream_t)stream);
+            if (rt != DYK_ERR_UNSUPPORTED) { DYK_LAUNCH_CHECK(); return rt; }
+        }
+        if (d->stride == 1 && d->k == 3) hipLaunchKernelGGL((dwconv_strip_kernel<f16_t, 3, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
+        else if (d->stride == 1 && d->k == 5) hipLaunchKernelGGL((dwconv_strip_kernel<f16_t, 5, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
+        else hipLaunchKernelGGL((dwconv_kernel<f16_t, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
+        DYK_LAUNCH_CHECK();
+        return DYK_OK;
+    }
     if (d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16 && dw_tile_on()) {
         const int rt = d->k == 3 ? launch_dw_tile<3, false>(d, (hipStream_t)stream) : launch_dw_tile<5, false>(d, (hipStream_t)stream);
         if (rt != DYK_ERR_UNSUPPORTED) { DYK_LAUNCH_CHECK(); return rt; }
@@ -1051,7 +1064,7 @@ extern "C" int dyk_dwconv_fwd(const DykDwDesc* d, void* stream) {
 extern "C" int dyk_dwconv_tile_ok(const DykDwDesc* d) {
     const int rc = check_dw(d);
     if (rc) return rc;
-    if (!(d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16 && dw_tile_on())) return 0;
+    if (!(d->stride == 1 && (d->k == 3 || d->k == 5) && (d->dtype == DYK_BF16 || d->dtype == DYK_F16) && dw_tile_on())) return 0;
     const int K = d->k, TW = 16, IC = TW + K - 1, NLD = K == 5 ? 8 : 6;
     const int CV = d->C / 8;
     const int groups = (CV + 7) / 8, CT = (CV + groups - 1) / groups;
@@ -1065,6 +1078,7 @@ extern "C" int dyk_dwconv_tile_ok(const DykDwDesc* d) {
 extern "C" int dyk_dwconv_dgrad(const DykDwDesc* d, void* stream) {
     const int rc = check_dw(d);
     if (rc) return rc;
+    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
     if (!d->w) return DYK_ERR_ARG;
     if (d->res) {                    // fused BatchNorm-backward reduce: LDS-tiled kernel only
         if (!d->bn || !d->stats || d->stats_slots <= 0 || d->ldr < d->C || d->ldr % 8 || ((uintptr_t)d->res % 16)) return DYK_ERR_ARG;
@@ -1111,6 +1125,7 @@ int launch_dw_wgrad(const DykDwDesc* d, hipStream_t s, int gx, int gy, int CVB) 
 extern "C" int dyk_dwconv_wgrad_rows(const DykDwDesc* d) {
     const int rc = check_dw(d);
     if (rc) return rc;
+    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
     const int epv = d->dtype == DYK_BF16 ? 8 : 4;
     DwWgTile c;
     if (dw_wgrad_tile_cfg(d, &c)) return c.P;
@@ -1122,6 +1137,7 @@ extern "C" int dyk_dwconv_wgrad_rows(const DykDwDesc* d) {
 extern "C" int dyk_dwconv_wgrad(const DykDwDesc* d, void* stream) {
     const int rc = check_dw(d);
     if (rc) return rc;
+    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
     if (!d->dw) return DYK_ERR_ARG;
     const int epv = d->dtype == DYK_BF16 ? 8 : 4;
     DwWgTile c;

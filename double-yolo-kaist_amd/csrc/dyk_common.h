@@ -1,9 +1,9 @@
 // Shared device helpers for the dyk HIP kernels (gfx950 / CDNA4 only).
 //
 // Data layout everywhere below the C ABI: activations are channels-last
-// ("NHWC"), element type T in {bf16 (raw uint16), f32}; a tensor is addressed
+// ("NHWC"), element type T in {bf16 (raw uint16), f16 (IEEE half, inference), f32}; a tensor is addressed
 // as base + pixel * ld + channel, with ld >= C so that a tensor can be a
-// channel slice of a wider (concat) buffer.  16-byte vectors (8 bf16 / 4 f32)
+// channel slice of a wider (concat) buffer.  16-byte vectors (8 bf16 or f16 / 4 f32)
 // are the unit of every global and LDS access.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,7 +54,76 @@ __device__ __host__ inline bf16_t f32_to_bf16(float f) {
     return (bf16_t)(u >> 16);
 }
 
+// ---------------------------------------------------------------- f16 <-> f32 (inference plans: DYK_F16)
+// IEEE half in raw storage.  A type of its own: bf16_t is a plain uint16_t, the kernel templates tell the two apart by type.
+struct f16_t { uint16_t v; };
+#define DYK_F16_MAX 65504.f
+// Every float -> f16 store SATURATES: clamp to +-65504, then round to nearest even (v_cvt_pk_f16_f32); NaN stays NaN,
+// denormals are kept.  An inf must never reach an activation buffer: the last K step of a pixel over-reads the next pixel's
+// first channels against zero weight rows (dyk/plan.py, kpad_bytes), and 0 x inf = NaN would land in finite outputs.
+// (compare + select, not v_min / v_max: those return the non-NaN operand)
+typedef __attribute__((ext_vector_type(2))) _Float16 dyk_f16x2_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+__device__ __host__ inline float f16_sat(float f) {
+    f = f > DYK_F16_MAX ? DYK_F16_MAX : f;
+    return f < -DYK_F16_MAX ? -DYK_F16_MAX : f;
+}
+__device__ inline uint32_t f32x2_to_f16x2(float lo, float hi) {
+    const dyk_f32x2_t v = {f16_sat(lo), f16_sat(hi)};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, dyk_f16x2_t));
+}
+__device__ __host__ inline float f16_to_f32(f16_t h) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (float)__builtin_bit_cast(_Float16, h.v);
+#endif
+    const uint32_t sign = ((uint32_t)h.v & 0x8000u) << 16, e = (h.v >> 10) & 0x1fu, m = h.v & 0x3ffu;
+    union { uint32_t u; float f; } c;
+    if (e == 0) {                                      // zero / denormal: m * 2^-24, exact in fp32
+        c.f = (float)m * (1.f / 16777216.f);
+        c.u |= sign;
+        return c.f;
+    }
+    c.u = sign | (e == 31 ? 0x7f800000u | (m << 13) : ((e + 112u) << 23) | (m << 13));
+    return c.f;
+}
+// host reference of the store rule above (bit-equal to clamp -> torch.half)
+__device__ __host__ inline f16_t f32_to_f16(float f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return f16_t{(uint16_t)(f32x2_to_f16x2(f, 0.f) & 0xffffu)};
+#endif
+    union { uint32_t u; float f; } c;
+    c.f = f;
+    const uint16_t sign = (uint16_t)((c.u >> 16) & 0x8000u);
+    const uint32_t a = c.u & 0x7fffffffu;
+    if (a > 0x7f800000u) return f16_t{(uint16_t)(sign | 0x7e00u | ((a >> 13) & 0x3ffu))};      // NaN (quiet)
+    if (a >= 0x477fe000u) return f16_t{(uint16_t)(sign | 0x7bffu)};                            // |f| >= 65504: saturate
+    if (a < 0x38800000u) {                                                                     // below 2^-14: denormal grid 2^-24
+        if (a < 0x33000000u) return f16_t{sign};                                               // < 2^-25 -> 0 (2^-25 itself: tie to even 0)
+        const uint32_t man = (a & 0x7fffffu) | 0x800000u;
+        const int sh = 126 - (int)(a >> 23);                                                   // 14 .. 24 (+ 0 extra bits)
+        const uint32_t q = man >> sh, rem = man & ((1u << sh) - 1u), half = 1u << (sh - 1);
+        return f16_t{(uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)))};
+    }
+    uint32_t u = a - 0x38000000u;                                                              // rebias 127 -> 15
+    u += 0xfffu + ((u >> 13) & 1u);
+    return f16_t{(uint16_t)(sign | (u >> 13))};
+}
+
+// the 16-bit storage type a kernel template writes when T is 16 bits wide (bf16_t in the fp32 instantiations, whose 16-bit
+// branches are compiled but never taken)
+template <typename T> struct Half16 { typedef bf16_t type; };
+template <> struct Half16<f16_t> { typedef f16_t type; };
+template <typename T> __device__ inline uint32_t f32x2_to_h2(float lo, float hi) {
+    if constexpr (__is_same(T, f16_t)) return f32x2_to_f16x2(lo, hi);
+    else return f32x2_to_bf16x2(lo, hi);
+}
+
 template <typename T> struct ElemTraits;
+template <> struct ElemTraits<f16_t> {
+    static constexpr int EPV = 8;
+    static __device__ inline float to_f32(f16_t v) { return f16_to_f32(v); }
+    static __device__ inline f16_t from_f32(float f) { return f32_to_f16(f); }
+};
 template <> struct ElemTraits<bf16_t> {
     static constexpr int EPV = 8;  // elements per 16-byte vector
     static __device__ inline float to_f32(bf16_t v) { return bf16_to_f32(v); }
@@ -91,6 +160,15 @@ template <> __device__ inline void vec_unpack<bf16_t>(const uint4& v, float* out
         out[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
     }
 }
+template <> __device__ inline void vec_unpack<f16_t>(const uint4& v, float* out) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const dyk_f16x2_t h = __builtin_bit_cast(dyk_f16x2_t, w[i]);
+        out[2 * i]     = (float)h[0];
+        out[2 * i + 1] = (float)h[1];
+    }
+}
 template <> __device__ inline void vec_unpack<float>(const uint4& v, float* out) {
     out[0] = __uint_as_float(v.x); out[1] = __uint_as_float(v.y);
     out[2] = __uint_as_float(v.z); out[3] = __uint_as_float(v.w);
@@ -100,6 +178,12 @@ template <> __device__ inline uint4 vec_pack<bf16_t>(const float* in) {
     uint32_t w[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[i] = f32x2_to_bf16x2(in[2 * i], in[2 * i + 1]);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+template <> __device__ inline uint4 vec_pack<f16_t>(const float* in) {
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = f32x2_to_f16x2(in[2 * i], in[2 * i + 1]);
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 template <> __device__ inline uint4 vec_pack<float>(const float* in) {

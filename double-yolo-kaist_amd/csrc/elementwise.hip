@@ -9,7 +9,7 @@ inline int ew_grid(long total_vec) {
     long g = (total_vec + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
-inline int epv_of(int dtype) { return dtype == DYK_BF16 ? 8 : 4; }
+inline int epv_of(int dtype) { return dtype == DYK_F32 ? 4 : 8; }
 
 // ------------------------------------------------------------------ axpby
 // out = sa*a (+ sb*b), sa = alpha * (p0 ? p0[0] : 1), sb = beta * (p1 ? p1[0] : 1).  alpha == 0: `a` is NOT read (the term is an
@@ -911,7 +911,7 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const float* __restri
 int check_ew(const DykEwDesc* d, bool need_b, bool need_out = true, bool twin_ok = false) {
     if (!d || !d->a || (need_out && !d->out) || (need_b && !d->b)) return DYK_ERR_ARG;
     if (d->twin && !twin_ok) return DYK_ERR_UNSUPPORTED;      // two-problem launches: BatchNorm passes and axpby only
-    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32) return DYK_ERR_ARG;
+    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32 && d->dtype != DYK_F16) return DYK_ERR_ARG;
     const int epv = epv_of(d->dtype);
     if (d->C <= 0 || d->C % epv || d->lda % epv || (need_out && d->ldo % epv) || (d->b && d->ldb % epv)) return DYK_ERR_ARG;
     return DYK_OK;
@@ -919,8 +919,18 @@ int check_ew(const DykEwDesc* d, bool need_b, bool need_out = true, bool twin_ok
 
 }  // namespace
 
+// DISPATCH_T: training kernels (bf16 | f32; f16 is the inference type: DYK_ERR_UNSUPPORTED); DISPATCH_TF: the forward
+// kernels an inference plan issues (bf16 | f16 | f32)
+#define DISPATCH_TF(kern, grid, block, lds, stream, ...)                                             \
+    do {                                                                                             \
+        if (d->dtype == DYK_BF16) hipLaunchKernelGGL(kern<bf16_t>, grid, block, lds, stream, __VA_ARGS__); \
+        else if (d->dtype == DYK_F16) hipLaunchKernelGGL(kern<f16_t>, grid, block, lds, stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kern<float>, grid, block, lds, stream, __VA_ARGS__);                 \
+        DYK_LAUNCH_CHECK();                                                                          \
+    } while (0)
 #define DISPATCH_T(kern, grid, block, lds, stream, ...)                                              \
     do {                                                                                             \
+        if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;                                         \
         if (d->dtype == DYK_BF16) hipLaunchKernelGGL(kern<bf16_t>, grid, block, lds, stream, __VA_ARGS__); \
         else hipLaunchKernelGGL(kern<float>, grid, block, lds, stream, __VA_ARGS__);                 \
         DYK_LAUNCH_CHECK();                                                                          \
@@ -934,7 +944,7 @@ extern "C" int dyk_axpby(const DykEwDesc* d, void* stream) {
     DykEwPair pr;
     const int nz = dyk_fill_ew_pair(pr, d);
     if (!nz) return DYK_ERR_ARG;
-    DISPATCH_T(axpby_kernel, dim3(grid, 1, nz), dim3(256), 0, (hipStream_t)stream, pr);
+    DISPATCH_TF(axpby_kernel, dim3(grid, 1, nz), dim3(256), 0, (hipStream_t)stream, pr);
     return DYK_OK;
 }
 
@@ -968,7 +978,7 @@ extern "C" int dyk_upsample2x_fwd(const DykEwDesc* d, void* stream) {
     if (rc) return rc;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0) return DYK_ERR_ARG;
     const int grid = ew_grid((long)d->B * d->H * d->W * 4 * (d->C / epv_of(d->dtype)));
-    DISPATCH_T(upsample2x_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
+    DISPATCH_TF(upsample2x_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
     return DYK_OK;
 }
 
@@ -981,20 +991,21 @@ extern "C" int dyk_upsample2x_bwd(const DykEwDesc* d, void* stream) {
     return DYK_OK;
 }
 
-#define MAXPOOL_K(kern, KK, arg)                                                                                  \
+#define MAXPOOL_K(kern, KK, arg, F16OK)                                                                                 \
     do {                                                                                                         \
+        if constexpr (F16OK) { if (d->dtype == DYK_F16) { hipLaunchKernelGGL((kern<f16_t, KK>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, arg); break; } } \
         if (d->dtype == DYK_BF16) hipLaunchKernelGGL((kern<bf16_t, KK>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, arg); \
         else hipLaunchKernelGGL((kern<float, KK>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, arg);      \
     } while (0)
-#define MAXPOOL_DISPATCH(kern, arg)                                                                               \
+#define MAXPOOL_DISPATCH(kern, arg, F16OK)                                                                              \
     do {                                                                                                         \
         switch (d->k) {                                                                                          \
-        case 2: MAXPOOL_K(kern, 2, arg); break;                                                                  \
-        case 3: MAXPOOL_K(kern, 3, arg); break;                                                                  \
-        case 5: MAXPOOL_K(kern, 5, arg); break;                                                                  \
-        case 9: MAXPOOL_K(kern, 9, arg); break;                                                                  \
-        case 13: MAXPOOL_K(kern, 13, arg); break;                                                                \
-        default: MAXPOOL_K(kern, 0, arg); break;                                                                 \
+        case 2: MAXPOOL_K(kern, 2, arg, F16OK); break;                                                                  \
+        case 3: MAXPOOL_K(kern, 3, arg, F16OK); break;                                                                  \
+        case 5: MAXPOOL_K(kern, 5, arg, F16OK); break;                                                                  \
+        case 9: MAXPOOL_K(kern, 9, arg, F16OK); break;                                                                  \
+        case 13: MAXPOOL_K(kern, 13, arg, F16OK); break;                                                                \
+        default: MAXPOOL_K(kern, 0, arg, F16OK); break;                                                                 \
         }                                                                                                        \
         DYK_LAUNCH_CHECK();                                                                                      \
     } while (0)
@@ -1012,13 +1023,14 @@ extern "C" int dyk_maxpool_fwd(const DykEwDesc* d, uint8_t* argmax, void* stream
     if (maxpool_tile_ok(d)) {
         const int HW = d->H * d->W, threads = maxpool_tile_threads(HW);
         const unsigned grid = (unsigned)(d->B * (d->C / epv_of(d->dtype)));
-        if (d->dtype == DYK_BF16) hipLaunchKernelGGL(maxpool_tile_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), (size_t)HW * 40, (hipStream_t)stream, *d, argmax);
+        if (d->dtype == DYK_F16) hipLaunchKernelGGL(maxpool_tile_fwd_kernel<f16_t>, dim3(grid), dim3(threads), (size_t)HW * 40, (hipStream_t)stream, *d, argmax);
+        else if (d->dtype == DYK_BF16) hipLaunchKernelGGL(maxpool_tile_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), (size_t)HW * 40, (hipStream_t)stream, *d, argmax);
         else hipLaunchKernelGGL(maxpool_tile_fwd_kernel<float>, dim3(grid), dim3(threads), (size_t)HW * 40, (hipStream_t)stream, *d, argmax);
         DYK_LAUNCH_CHECK();
         return DYK_OK;
     }
     const int grid = ew_grid((long)d->B * d->H * d->W * (d->C / epv_of(d->dtype)));
-    MAXPOOL_DISPATCH(maxpool_fwd_kernel, argmax);
+    MAXPOOL_DISPATCH(maxpool_fwd_kernel, argmax, true);
     return DYK_OK;
 }
 
@@ -1026,6 +1038,7 @@ extern "C" int dyk_maxpool_bwd(const DykEwDesc* d, const uint8_t* argmax, void* 
     const int rc = check_ew(d, false);
     if (rc) return rc;
     if (!argmax || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->k <= 0 || d->k > 15 || d->slots < 0 || d->slots > 8) return DYK_ERR_ARG;
+    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
     if (maxpool_tile_ok(d)) {
         const int HW = d->H * d->W, threads = maxpool_tile_threads(HW);
         const unsigned grid = (unsigned)(d->B * (d->C / epv_of(d->dtype)));
@@ -1035,7 +1048,7 @@ extern "C" int dyk_maxpool_bwd(const DykEwDesc* d, const uint8_t* argmax, void* 
         return DYK_OK;
     }
     const int grid = ew_grid((long)d->B * d->H * d->W * (d->C / epv_of(d->dtype)));
-    MAXPOOL_DISPATCH(maxpool_bwd_kernel, argmax);
+    MAXPOOL_DISPATCH(maxpool_bwd_kernel, argmax, false);       // (f16 refused above: no backward forms)
     return DYK_OK;
 }
 
@@ -1054,7 +1067,7 @@ extern "C" int dyk_se_pool(const DykEwDesc* d, float* pooled, void* stream) {
         const long hw = (long)d->H * d->W;
         while (HS < DYK_SE_POOL_SPLITS && (long)gx * d->B * HS < 1024 && hw / (HS * 2) >= (long)PY * 8) HS <<= 1;
     }
-    DISPATCH_T(se_pool_kernel, dim3(gx, d->B, HS), dim3(256), 0, (hipStream_t)stream, *d, pooled, CVB);
+    DISPATCH_TF(se_pool_kernel, dim3(gx, d->B, HS), dim3(256), 0, (hipStream_t)stream, *d, pooled, CVB);
     if (HS > 1) {
         const int n = d->B * d->C;
         hipLaunchKernelGGL(se_pool_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)d->aux2,
@@ -1128,6 +1141,7 @@ extern "C" int dyk_se_scale(const DykEwDesc* d, void* stream) {
     if (gy < 1) gy = 1;
     dim3 grid(gx, (int)gy, d->B);
     if (d->red) {          // with the BatchNorm-backward reduce of the producer of `out`'s tensor (see the kernel)
+        if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
         if (!d->b || !d->p2 || d->ldb % epv_of(d->dtype)) return DYK_ERR_ARG;
         long nz = 768 / ((long)gx * gy);                 // ~3 workgroups per CU, each over B / nz images
         if (nz < 1) nz = 1;
@@ -1149,7 +1163,8 @@ extern "C" int dyk_se_scale(const DykEwDesc* d, void* stream) {
         DYK_LAUNCH_CHECK();
         return DYK_OK;
     }
-    if (d->dtype == DYK_BF16) hipLaunchKernelGGL((se_scale_kernel<bf16_t, -2>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
+    if (d->dtype == DYK_F16) hipLaunchKernelGGL((se_scale_kernel<f16_t, -2>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
+    else if (d->dtype == DYK_BF16) hipLaunchKernelGGL((se_scale_kernel<bf16_t, -2>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
     else hipLaunchKernelGGL((se_scale_kernel<float, -2>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
     DYK_LAUNCH_CHECK();
     return DYK_OK;
@@ -1238,6 +1253,8 @@ extern "C" int dyk_patch_gather(const float* in, void* out, int32_t B, int32_t C
     const int grid = ew_grid((long)B * Ho * Wo);
     if (dtype == DYK_BF16)
         hipLaunchKernelGGL(patch_gather_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (bf16_t*)out, B, Cin, H, W, k, stride, pad, Ho, Wo, ld, mul);
+    else if (dtype == DYK_F16)
+        hipLaunchKernelGGL(patch_gather_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (f16_t*)out, B, Cin, H, W, k, stride, pad, Ho, Wo, ld, mul);
     else if (dtype == DYK_F32)
         hipLaunchKernelGGL(patch_gather_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (float*)out, B, Cin, H, W, k, stride, pad, Ho, Wo, ld, mul);
     else

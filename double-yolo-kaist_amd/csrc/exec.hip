@@ -18,8 +18,8 @@ __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ src
         const float4 v = ((const float4*)src)[i];
         if (sizeof(T) == 2) {
             uint2 pk;
-            pk.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);
-            pk.y = (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16);
+            pk.x = f32x2_to_h2<T>(v.x, v.y);
+            pk.y = f32x2_to_h2<T>(v.z, v.w);
             ((uint2*)dst)[i] = pk;
         } else {
             ((float4*)dst)[i] = v;
@@ -166,6 +166,8 @@ extern "C" int dyk_cast_f32(const float* src, void* dst, int64_t n, int32_t dtyp
     const int grid = grid_for(n / 4 + 1, 256);
     if (dtype == DYK_BF16)
         hipLaunchKernelGGL(cast_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, (long)n);
+    else if (dtype == DYK_F16)
+        hipLaunchKernelGGL(cast_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (f16_t*)dst, (long)n);
     else if (dtype == DYK_F32)
         hipLaunchKernelGGL(cast_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (float*)dst, (long)n);
     else
@@ -180,6 +182,8 @@ extern "C" int dyk_cast_pad_rows(const float* src, void* dst, int32_t R, int32_t
     const int grid = grid_for((long)R * Cpad, 256);
     if (dtype == DYK_BF16)
         hipLaunchKernelGGL(cast_pad_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, R, C, Cpad);
+    else if (dtype == DYK_F16)
+        hipLaunchKernelGGL(cast_pad_rows_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (f16_t*)dst, R, C, Cpad);
     else if (dtype == DYK_F32)
         hipLaunchKernelGGL(cast_pad_rows_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (float*)dst, R, C, Cpad);
     else
@@ -192,6 +196,8 @@ extern "C" int dyk_cast_pad_table(const DykPadEntry* tab, int32_t n_entries, int
     if (!tab || n_entries <= 0 || total_blocks <= 0) return DYK_ERR_ARG;
     if (dtype == DYK_BF16)
         hipLaunchKernelGGL(cast_pad_table_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, tab, n_entries);
+    else if (dtype == DYK_F16)
+        hipLaunchKernelGGL(cast_pad_table_kernel<f16_t>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, tab, n_entries);
     else if (dtype == DYK_F32)
         hipLaunchKernelGGL(cast_pad_table_kernel<float>, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, tab, n_entries);
     else
@@ -205,6 +211,8 @@ extern "C" int dyk_transpose_taps(const float* src, void* dst, const DykTranspos
     if (!src || !dst || !tab || n_entries <= 0 || total_tiles <= 0) return DYK_ERR_ARG;
     if (dtype == DYK_BF16)
         hipLaunchKernelGGL(transpose_taps_kernel<bf16_t>, dim3((total_tiles + TRANSPOSE_RUN - 1) / TRANSPOSE_RUN), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, tab, n_entries, total_tiles);
+    else if (dtype == DYK_F16)
+        hipLaunchKernelGGL(transpose_taps_kernel<f16_t>, dim3((total_tiles + TRANSPOSE_RUN - 1) / TRANSPOSE_RUN), dim3(256), 0, (hipStream_t)stream, src, (f16_t*)dst, tab, n_entries, total_tiles);
     else if (dtype == DYK_F32)
         hipLaunchKernelGGL(transpose_taps_kernel<float>, dim3((total_tiles + TRANSPOSE_RUN - 1) / TRANSPOSE_RUN), dim3(256), 0, (hipStream_t)stream, src, (float*)dst, tab, n_entries, total_tiles);
     else

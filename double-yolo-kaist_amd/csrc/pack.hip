@@ -76,6 +76,8 @@ extern "C" int dyk_pack_conv_weight(const float* w, void* out, int32_t Cout, int
     hipStream_t s = (hipStream_t)stream;
     if (dtype == DYK_BF16)
         hipLaunchKernelGGL(pack_weight_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, w, (bf16_t*)out, Cout, Cin, taps, R, C, transposed);
+    else if (dtype == DYK_F16)
+        hipLaunchKernelGGL(pack_weight_kernel<f16_t>, dim3(grid), dim3(256), 0, s, w, (f16_t*)out, Cout, Cin, taps, R, C, transposed);
     else if (dtype == DYK_F32)
         hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(grid), dim3(256), 0, s, w, (float*)out, Cout, Cin, taps, R, C, transposed);
     else
@@ -92,6 +94,8 @@ extern "C" int dyk_nchw_to_nhwc(const float* in, void* out, int32_t B, int32_t C
     hipStream_t s = (hipStream_t)stream;
     if (dtype == DYK_BF16)
         hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, grid, dim3(256), 0, s, in, (bf16_t*)out, C, HW, Cpad, ldo, mul);
+    else if (dtype == DYK_F16)
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<f16_t>, grid, dim3(256), 0, s, in, (f16_t*)out, C, HW, Cpad, ldo, mul);
     else if (dtype == DYK_F32)
         hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, s, in, (float*)out, C, HW, Cpad, ldo, mul);
     else
@@ -108,6 +112,8 @@ extern "C" int dyk_nhwc_to_nchw(const void* in, float* out, int32_t B, int32_t C
     hipStream_t s = (hipStream_t)stream;
     if (dtype == DYK_BF16)
         hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)in, out, C, HW, ldi);
+    else if (dtype == DYK_F16)
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)in, out, C, HW, ldi);
     else if (dtype == DYK_F32)
         hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, s, (const float*)in, out, C, HW, ldi);
     else

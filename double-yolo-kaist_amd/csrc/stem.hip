@@ -91,12 +91,12 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const DykStemDesc d, cons
             }
         }
         if (sizeof(T) == 2) {
-            bf16_t* yp = (bf16_t*)d.y + (long)p * d.ldy;
+            uint16_t* yp = (uint16_t*)d.y + (long)p * d.ldy;
 #pragma unroll
             for (int c = 0; c < COUT; c += 8) {
                 uint4 pk;
-                pk.x = f32x2_to_bf16x2(acc[c + 0], acc[c + 1]); pk.y = f32x2_to_bf16x2(acc[c + 2], acc[c + 3]);
-                pk.z = f32x2_to_bf16x2(acc[c + 4], acc[c + 5]); pk.w = f32x2_to_bf16x2(acc[c + 6], acc[c + 7]);
+                pk.x = f32x2_to_h2<T>(acc[c + 0], acc[c + 1]); pk.y = f32x2_to_h2<T>(acc[c + 2], acc[c + 3]);
+                pk.z = f32x2_to_h2<T>(acc[c + 4], acc[c + 5]); pk.w = f32x2_to_h2<T>(acc[c + 6], acc[c + 7]);
                 *(uint4*)(yp + c) = pk;
             }
         } else {
@@ -143,7 +143,9 @@ constexpr int STEM_SEG = 128;      // output pixels of one row per staged segmen
 //     as four runs of four: packed conversion, four ds_write_b64 into an 80-byte-pitch pixel row, two ds_read_b128 + two
 //     16-byte global stores per lane (whole 64-byte pixels, consecutive pixels contiguous);
 //   * BatchNorm statistics per lane and filter in registers across all tiles, folded over the pixels (lanes) once per wave.
-template <int STRIDE, bool AFF, bool STATS>
+// TO = 16-bit type of the output (bf16 | f16).  The arithmetic is the same for both -- pixel values and the three weight
+// terms are exact in bf16, sums in fp32 (the stem is an fp32 island of the 16-bit plans) -- only the store conversion differs.
+template <int STRIDE, bool AFF, bool STATS, typename TO = bf16_t>
 __global__ __launch_bounds__(64) void stem_fwd_u8t_kernel(const DykStemDesc d, const float* __restrict__ wt, int segs_per_wg,
                                                           int segs_per_row, int nsegs) {
     typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_v;
@@ -277,8 +279,8 @@ __global__ __launch_bounds__(64) void stem_fwd_u8t_kernel(const DykStemDesc d, c
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 uint2 pk;
-                pk.x = f32x2_to_bf16x2(v[4 * q], v[4 * q + 1]);
-                pk.y = f32x2_to_bf16x2(v[4 * q + 2], v[4 * q + 3]);
+                pk.x = f32x2_to_h2<TO>(v[4 * q], v[4 * q + 1]);
+                pk.y = f32x2_to_h2<TO>(v[4 * q + 2], v[4 * q + 3]);
                 *(uint2*)(wptr + 16 * q) = pk;
             }
             __syncthreads();
@@ -628,7 +630,7 @@ int check(const DykStemDesc* d) {
     if (!d || !d->img || d->B <= 0 || d->H <= 0 || d->W <= 0) return DYK_ERR_ARG;
     if (d->k != 3 || d->pad != 1 || (d->stride != 1 && d->stride != 2)) return DYK_ERR_UNSUPPORTED;
     if (d->Cout != 16 && d->Cout != 32) return DYK_ERR_UNSUPPORTED;
-    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32) return DYK_ERR_ARG;
+    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32 && d->dtype != DYK_F16) return DYK_ERR_ARG;
     if ((long)d->B * d->H * d->W * 3 >= (1L << 31)) return DYK_ERR_ARG;       // 32-bit pixel indices
     if (d->Ho != (d->H + 2 - 3) / d->stride + 1 || d->Wo != (d->W + 2 - 3) / d->stride + 1) return DYK_ERR_ARG;
     return DYK_OK;
@@ -643,7 +645,10 @@ template <typename K> static inline void stem_allow_lds(K kfn, size_t bytes) {
 #define STEM_DISPATCH_LDS(KERNEL, grid, LDSB, ...)                                                                   \
     do {                                                                                                              \
         const bool u8 = d->in_u8 != 0;                                                                                \
-        if (d->dtype == DYK_BF16) {                                                                                   \
+        if (d->dtype == DYK_F16) {                                                                                    \
+            if (d->Cout == 32) { if (u8) hipLaunchKernelGGL((KERNEL<f16_t, 32, true>), grid, dim3(256), LDSB, s, __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<f16_t, 32, false>), grid, dim3(256), LDSB, s, __VA_ARGS__); } \
+            else               { if (u8) hipLaunchKernelGGL((KERNEL<f16_t, 16, true>), grid, dim3(256), LDSB, s, __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<f16_t, 16, false>), grid, dim3(256), LDSB, s, __VA_ARGS__); } \
+        } else if (d->dtype == DYK_BF16) {                                                                            \
             if (d->Cout == 32) { if (u8) { stem_allow_lds(KERNEL<bf16_t, 32, true>, LDSB); hipLaunchKernelGGL((KERNEL<bf16_t, 32, true>), grid, dim3(256), LDSB, s, __VA_ARGS__); } else { stem_allow_lds(KERNEL<bf16_t, 32, false>, LDSB); hipLaunchKernelGGL((KERNEL<bf16_t, 32, false>), grid, dim3(256), LDSB, s, __VA_ARGS__); }; } \
             else               { if (u8) { stem_allow_lds(KERNEL<bf16_t, 16, true>, LDSB); hipLaunchKernelGGL((KERNEL<bf16_t, 16, true>), grid, dim3(256), LDSB, s, __VA_ARGS__); } else { stem_allow_lds(KERNEL<bf16_t, 16, false>, LDSB); hipLaunchKernelGGL((KERNEL<bf16_t, 16, false>), grid, dim3(256), LDSB, s, __VA_ARGS__); }; } \
         } else {                                                                                                      \
@@ -667,11 +672,25 @@ template <typename K> static inline void stem_allow_lds(K kfn, size_t bytes) {
 extern "C" int dyk_stem_conv_fwd(const DykStemDesc* d, void* stream) {
     const int rc = check(d);
     if (rc) return rc;
-    if (!d->wt || !d->y || d->ldy < d->Cout || (d->ldy * (d->dtype == DYK_BF16 ? 2 : 4)) % 16 || ((uintptr_t)d->y % 16)) return DYK_ERR_ARG;
+    if (!d->wt || !d->y || d->ldy < d->Cout || (d->ldy * (d->dtype == DYK_F32 ? 4 : 2)) % 16 || ((uintptr_t)d->y % 16)) return DYK_ERR_ARG;
+    if (d->dtype == DYK_F16 && d->stats) return DYK_ERR_UNSUPPORTED;          // (f16 is the inference type: no BatchNorm statistics)
     hipStream_t s = (hipStream_t)stream;
     const long npix = (long)d->B * d->Ho * d->Wo;
     constexpr bool fast = true;
     // (16 filters / stride 2 -- the MobileNet stem -- measured faster in the scalar kernel: half of the 32-wide tile idles)
+    if (fast && d->in_u8 && d->dtype == DYK_F16 && d->Cout == 32 && d->W % 4 == 0 && ((uintptr_t)d->img % 4) == 0 && (d->stride == 1 || d->stride == 2)) {
+        const int segs_per_row = (d->Wo + STEM_SEG - 1) / STEM_SEG;
+        const long nsegs = (long)d->B * d->Ho * segs_per_row;
+        const long want = nsegs < 3072 ? nsegs : 3072;
+        const int spw = (int)((nsegs + want - 1) / want);
+        const dim3 grid((unsigned)((nsegs + spw - 1) / spw));
+#define DYK_STEM_H(S_, A_) hipLaunchKernelGGL((stem_fwd_u8t_kernel<S_, A_, false, f16_t>), grid, dim3(64), 0, s, *d, d->wt, spw, segs_per_row, (int)nsegs)
+        if (d->stride == 1) { if (d->scale) DYK_STEM_H(1, true); else DYK_STEM_H(1, false); }
+        else { if (d->scale) DYK_STEM_H(2, true); else DYK_STEM_H(2, false); }
+#undef DYK_STEM_H
+        DYK_LAUNCH_CHECK();
+        return DYK_OK;
+    }
     if (fast && d->in_u8 && d->dtype == DYK_BF16 && d->Cout == 32 && d->W % 4 == 0 && ((uintptr_t)d->img % 4) == 0 && (d->stride == 1 || d->stride == 2)) {
         const int segs_per_row = (d->Wo + STEM_SEG - 1) / STEM_SEG;
         const long nsegs = (long)d->B * d->Ho * segs_per_row;
@@ -727,6 +746,7 @@ extern "C" int dyk_stem_conv_wgrad(const DykStemDesc* d, void* stream) {
     const int rc = check(d);
     if (rc) return rc;
     if (d->bn_fused && !dyk_stem_wgrad_bn_fusable(d)) return DYK_ERR_UNSUPPORTED;
+    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
     if ((!d->dy && !d->bn_fused) || !d->dw || !d->part || d->lddy < d->Cout) return DYK_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const long npix = (long)d->B * d->Ho * d->Wo;

@@ -16,8 +16,10 @@ from .plan import compile_plan
 def _compute_dtype(model):
     forced = getattr(model, "dyk_dtype", None) or os.environ.get("DYK_DTYPE")
     if forced:
+        # fp16 (IEEE half, saturating stores): inference plans only -- opt-in here, never selected by an autocast region
         return {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32, "f32": torch.float32,
-                "float32": torch.float32}[str(forced).replace("torch.", "")]
+                "float32": torch.float32, "fp16": torch.float16, "float16": torch.float16, "half": torch.float16,
+                "f16": torch.float16}[str(forced).replace("torch.", "")]
     # the reference trains under torch.cuda.amp.autocast (kaist_train_eval_utils.py:74); any autocast
     # region selects the reduced-precision path, which on MI355X is bf16 MFMA with fp32 accumulation
     if torch.is_autocast_enabled():
@@ -31,7 +33,8 @@ def _compute_dtype(model):
             warnings.warn("dyk: the autocast region asks for %s (the reference trains under fp16 autocast + GradScaler, "
                           "kaist_train_eval_utils.py:74); the MI355X path computes reduced precision in bfloat16 MFMA with "
                           "fp32 accumulation instead -- same storage width, wider exponent, so loss scaling is a no-op.  "
-                          "Set model.dyk_dtype = 'fp32' for bit-level comparisons against an fp32 reference run." % ac)
+                          "Set model.dyk_dtype = 'fp32' for bit-level comparisons against an fp32 reference run, or "
+                          "model.dyk_dtype = 'fp16' for fp16 inference (eval only: 11 significant bits, saturating stores)." % ac)
         return torch.bfloat16
     return torch.float32
 

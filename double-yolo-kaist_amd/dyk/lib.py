@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(os.path.dirname(_HERE), "csrc")
 LIB_PATH = os.path.join(CSRC_DIR, "libdyk_hip.so")
 
-DYK_F32, DYK_BF16, DYK_U8 = 0, 1, 2
+DYK_F32, DYK_BF16, DYK_U8, DYK_F16 = 0, 1, 2, 3       # DYK_F16: inference plans only (forward kernels)
 ACT_CODES = {"linear": 0, "leaky": 1, "mish": 2, "relu": 3, "relu6": 4, "hard-sigmoid": 5, "hard-swish": 6}
 EPI_AFFINE, EPI_RESIDUAL, EPI_STATS, EPI_ACCUM, EPI_OUT_F32, EPI_BNBWD, EPI_ADDEND, EPI_BNFWD = 1, 2, 4, 8, 16, 32, 64, 128
 EW_ACCUM = 1

@@ -1,7 +1,7 @@
 """Operator-level wrappers over the C ABI (one Python function per libdyk_hip.so entry point).
 
 Tensors are torch CUDA tensors used purely as device-memory handles: channels-last
-``[B, H, W, C]`` (bf16 or f32), possibly a channel slice of a wider buffer.  Nothing here
+``[B, H, W, C]`` (bf16, f16 or f32), possibly a channel slice of a wider buffer.  Nothing here
 computes with torch; a missing library or a CPU tensor raises.
 """
 import ctypes
@@ -9,16 +9,18 @@ import ctypes
 import torch
 
 from . import lib as _l
-from .lib import (ACT_CODES, DYK_BF16, DYK_F32, EPI_ACCUM, EPI_AFFINE, EPI_OUT_F32, EPI_RESIDUAL, EPI_STATS,
+from .lib import (ACT_CODES, DYK_BF16, DYK_F16, DYK_F32, EPI_ACCUM, EPI_AFFINE, EPI_OUT_F32, EPI_RESIDUAL, EPI_STATS,
                   DykConvDesc, DykWgradDesc, check, load)
 
 
 def dtype_code(dt):
     if dt == torch.bfloat16:
         return DYK_BF16
+    if dt == torch.float16:
+        return DYK_F16
     if dt == torch.float32:
         return DYK_F32
-    raise TypeError("dyk supports bf16 and f32 activations, got %s" % dt)
+    raise TypeError("dyk supports bf16, f16 (inference) and f32 activations, got %s" % dt)
 
 
 def _stream():

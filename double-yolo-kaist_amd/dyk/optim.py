@@ -194,7 +194,9 @@ class _FusedBase(torch.optim.Optimizer):
             side = self._side
             st.compute_weights(torch.bfloat16, skip_cast=self._wc_complete, side=side)
         for dt in list(st._compute):
-            if dt != torch.bfloat16:
+            # (the fp16 copy serves inference plans only: mark_dirty() above made it stale, and the next fp16 forward rebuilds it
+            # through the version check of compute_weights -- no cast per training step for a copy an evaluation left behind)
+            if dt not in (torch.bfloat16, torch.float16):
                 st.compute_weights(dt)
 
     # ------------------------------------------------------------------ checkpoint format of torch.optim

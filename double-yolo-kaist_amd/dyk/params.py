@@ -250,7 +250,7 @@ class ParamStore:
             else:
                 self.wt_ready = None
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        code = L.DYK_BF16 if dtype == torch.bfloat16 else L.DYK_F32
+        code = {torch.bfloat16: L.DYK_BF16, torch.float16: L.DYK_F16}.get(dtype, L.DYK_F32)
         if st is None:
             st = self._alloc(dtype)
             self._compute[dtype] = st
@@ -263,7 +263,7 @@ class ParamStore:
             side.wait_event(here)
             tstream = ctypes.c_void_p(side.cuda_stream)
         for (tab, n, tiles), dst in zip(self._transpose_table(), (st["Wt"], st["Wt_pad"])):
-            if n:
+            if n and dtype != torch.float16:       # (only data gradients read the tap-major packs: never an fp16 plan)
                 check(lib.dyk_transpose_taps(self.P.data_ptr(), dst.data_ptr(), tab.data_ptr(), n, tiles, code, tstream),
                       "dyk_transpose_taps")
         if side is not None:
@@ -274,7 +274,7 @@ class ParamStore:
         # nearly idle GPU on the caller's stream at every step boundary)
         tab = st.get("pad_table")
         if tab is None:
-            esz = 2 if dtype == torch.bfloat16 else 4
+            esz = 4 if dtype == torch.float32 else 2
             ents = []
             for name, off in st["fwd_pad_off"].items():
                 e = self.by_name[name]

@@ -226,9 +226,15 @@ class Plan:
 def compile_plan(model, store, B, H, W, dtype, training, device, dry=False):
     """model: models.YOLO ; store: ParamStore (adopted on `device`).  dry=True resolves shapes, buffers
     and command lists without touching the GPU library (host-logic tests run it on the CPU)."""
+    if dtype == torch.float16 and training:
+        raise NotImplementedError("fp16 is an inference mode (model.eval()): training runs in bf16 or fp32 -- the backward, "
+                                  "weight-gradient and BatchNorm-statistics kernels are not built for fp16")
     cw = store.alloc_compute(dtype) if dry else store.compute_weights(dtype)
-    code = L.DYK_BF16 if dtype == torch.bfloat16 else L.DYK_F32
-    es = 2 if dtype == torch.bfloat16 else 4
+    # 16-bit element types: bf16 (training and inference) and fp16 (inference only; the bf16 eval plan with the element type
+    # swapped).  Decisions about sizes, tiles and candidates go by the element size; decisions about training (statistics
+    # epilogues, fused BatchNorm forms) stay on `code == L.DYK_BF16`.
+    code = {torch.bfloat16: L.DYK_BF16, torch.float16: L.DYK_F16}.get(dtype, L.DYK_F32)
+    es = 4 if dtype == torch.float32 else 2
     plan = Plan()
     act_arena, grad_arena, ws, st_arena = Arena("act"), Arena("grad"), Arena("ws"), Arena("stats")
     plan.arenas = {"act": act_arena, "grad": grad_arena, "ws": ws, "stats": st_arena}
@@ -1587,7 +1593,7 @@ def _fuse_late_reduces(plan, store):
     for ri, (op, r) in enumerate(cmds):
         if op != L.OP_BN_BWD_REDUCE:
             continue
-        es = 2 if r.dtype == L.DYK_BF16 else 4
+        es = 2 if r.dtype in _H16 else 4
         target = mem.block(r.a, r.lda * es, r.C * es)
         if target is None:
             continue
@@ -1993,10 +1999,15 @@ def _tune_cache_save():
         pass
 
 
+_H16 = (L.DYK_BF16, L.DYK_F16)          # the 16-bit element types: one candidate set (the tune key carries d.dtype)
+
+
 def pw_eligible(d):
     """mirror of conv_pw_eligible (csrc/conv_pw_kernel.h): 1x1 / stride 1 / dense grid, bf16, K <= 256, plain | statistics |
     BatchNorm-backward (| chain) epilogues, weights of one 128-row channel tile <= 64 KB"""
-    if d.dtype != L.DYK_BF16 or d.ntaps != 1 or d.tdy[0] or d.tdx[0] or d.ncls > 1 or d.twin or d.splitk > 1:
+    if d.dtype == L.DYK_F16 and d.flags != 0:          # (fp16, the inference type: the plain store only)
+        return False
+    if d.dtype not in _H16 or d.ntaps != 1 or d.tdy[0] or d.tdx[0] or d.ncls > 1 or d.twin or d.splitk > 1:
         return False
     if (d.isy, d.isx, d.osy, d.osx, d.ooy, d.oox) != (1, 1, 1, 1, 0, 0):
         return False
@@ -2011,12 +2022,12 @@ def pw_eligible(d):
 
 def _conv_candidates(d):
     """tile configurations of dyk_conv_igemm for one problem: K-step bytes | ring stages << 8 | pixel tile << 12
-    (0 = 128, 1 = 80, 2 = 160 pixels, 3 / 4 = halo kernel 4x20 / 8x20; bf16 only) | channel tile << 24 (0 = by Cout, 2 = 64, 1 = 32)
+    (0 = 128, 1 = 80, 2 = 160 pixels, 3 / 4 = halo kernel 4x20 / 8x20; 16-bit types only) | channel tile << 24 (0 = by Cout, 2 = 64, 1 = 32)
     | 1 << 28 = K-grouped workgroups"""
-    es = 2 if d.dtype == L.DYK_BF16 else 4
+    es = 2 if d.dtype in _H16 else 4
     bkbs = [64] + ([128] if (d.Cin * es) % 128 == 0 else [])
-    tiles = [0, 1, 2] if d.dtype == L.DYK_BF16 else [0]
-    if (d.dtype == L.DYK_BF16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi
+    tiles = [0, 1, 2] if d.dtype in _H16 else [0]
+    if (d.dtype in _H16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi
             and d.Wi % 20 == 0 and d.Hi % 4 == 0):
         tiles += [3] + ([4] if d.Hi % 8 == 0 else [])       # 3x3 halo kernel, 4x20 / 8x20 pixel patches
     bms = [0] + ([2] if d.Cout > 64 else ([1] if d.Cout > 32 else []))
@@ -2030,7 +2041,7 @@ def _conv_candidates(d):
                     if t in (3, 4) and pipe != 2:
                         continue                      # the halo kernel has a fixed pipeline
                     out.append(bkb | (pipe << 8) | (t << 12) | (bm << 24))
-    if (d.dtype == L.DYK_BF16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi and d.ncls <= 1
+    if (d.dtype in _H16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi and d.ncls <= 1
             and d.Cin % 32 == 0 and d.Wi % 20 == 0 and not (d.flags & (L.EPI_OUT_F32 | L.EPI_BNFWD))
             and os.environ.get("DYK_CONV_LT", "1") != "0"):
         # large-tile 3x3 kernels (csrc/conv_lt_kernel.h): 8 waves, 128 x 320 / 256 x 160 / 128 x 160 with two K-groups, halo patch of
@@ -2054,7 +2065,7 @@ def _conv_candidates(d):
                 out.append((7 << 12) | (nxs << 8) | (1 << 24))
             else:
                 out.append((7 << 12) | (nxs << 8) | (1 << 25))
-    if d.dtype == L.DYK_BF16 and (d.Cin * es) % 128 == 0 and d.Cin >= 128 and os.environ.get("DYK_CONV_KG", "1") != "0":
+    if d.dtype in _H16 and (d.Cin * es) % 128 == 0 and d.Cin >= 128 and os.environ.get("DYK_CONV_KG", "1") != "0":
         # K-grouped workgroups (two 4-wave groups over the two halves of Cin): for tiles that leave a CU one workgroup
         for t in (1, 2):
             for bm in bms:
@@ -2073,7 +2084,7 @@ def _conv_split_candidates(d):
         return []
     if d.twin or d.ncls > 1 or d.flags & L.EPI_BNFWD:
         return []
-    es = 2 if d.dtype == L.DYK_BF16 else 4
+    es = 2 if d.dtype in _H16 else 4
     npix = d.B * d.Hg * d.Wg
     max_s = 8                # (12 / 16 slices measured equal to 8 at batch 1, round 5)
     out = []
@@ -2084,7 +2095,7 @@ def _conv_split_candidates(d):
     if (d.Cin * es) % 64:
         return []
     bkbs = [128] if (d.Cin * es) % 128 == 0 else [64]
-    tiles_px = [(2, 160), (0, 128), (1, 80)] if d.dtype == L.DYK_BF16 else [(0, 128)]
+    tiles_px = [(2, 160), (0, 128), (1, 80)] if d.dtype in _H16 else [(0, 128)]
     bms = [(0, 128 if d.Cout > 64 else (64 if d.Cout > 32 else 32))] + ([(2, 64)] if d.Cout > 64 else [])
     for bkb in bkbs:
         kch = (d.Cin * es) // bkb
@@ -2096,9 +2107,9 @@ def _conv_split_candidates(d):
                 for s in splits(tiles, kch):
                     for pipe in (2, 3):
                         out.append((bkb | (pipe << 8) | (t << 12) | (bmc << 24), s))
-                    if d.dtype == L.DYK_BF16 and bkb == 128 and t in (1, 2) and bm >= 64 and kch // s >= 4 and os.environ.get("DYK_CONV_KG", "1") != "0":
+                    if d.dtype in _H16 and bkb == 128 and t in (1, 2) and bm >= 64 and kch // s >= 4 and os.environ.get("DYK_CONV_KG", "1") != "0":
                         out.append((128 | (2 << 8) | (t << 12) | (bmc << 24) | (1 << 28), s))
-    if (d.dtype == L.DYK_BF16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi
+    if (d.dtype in _H16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi
             and d.Cin % 32 == 0 and d.Wi % 20 == 0 and not (d.flags & L.EPI_OUT_F32) and os.environ.get("DYK_CONV_LT", "1") != "0"):
         for shape, (bm, bn, kg) in ((1, (128, 320, 1)), (2, (256, 160, 1)), (3, (128, 160, 2))):
             if shape == 2 and d.Cout < 256:

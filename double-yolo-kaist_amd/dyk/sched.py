@@ -109,7 +109,7 @@ class Memory:
 
 
 def _es(code):
-    return 2 if code == L.DYK_BF16 else 4
+    return 2 if code in (L.DYK_BF16, L.DYK_F16) else 4
 
 
 def _v(p):

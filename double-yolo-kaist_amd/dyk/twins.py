@@ -150,7 +150,7 @@ def worth_pairing(op, d, plan, mode, max_bytes):
     e = plan._desc_at[d.p[1]] if op == L.OP_BN_FWD_FUSED else d
     if op == L.OP_BN_FINALIZE:
         return True
-    es = 2 if e.dtype == L.DYK_BF16 else 4
+    es = 2 if e.dtype in (L.DYK_BF16, L.DYK_F16) else 4
     return float(e.npix) * e.C * es <= max_bytes
 
 

@@ -17,8 +17,9 @@
  *     nothing calls exit().
  *   - activations are channels-last: element (b, y, x, c) of a tensor lives at
  *     base + ((b*H + y)*W + x)*ld + c with ld >= C (ld > C when the tensor is a
- *     channel slice of a concat buffer).  dtype is DYK_BF16 (raw uint16) or DYK_F32.
- *     Channel counts, ld and channel offsets must be multiples of 8 (bf16) / 4 (f32)
+ *     channel slice of a concat buffer).  dtype is DYK_BF16 (raw uint16), DYK_F16 (raw IEEE half;
+ *     forward / inference kernels only) or DYK_F32.
+ *     Channel counts, ld and channel offsets must be multiples of 8 (bf16, f16) / 4 (f32)
  *     so that every pixel row starts 16-byte aligned.
  */
 #ifndef DYK_HIP_H
@@ -40,7 +41,9 @@ enum {
     DYK_ERR_STATE = -4     /* plan used before bind, etc. */
 };
 
-enum { DYK_F32 = 0, DYK_BF16 = 1, DYK_U8 = 2 /* image input of dyk_image_prep only */ };
+enum { DYK_F32 = 0, DYK_BF16 = 1, DYK_U8 = 2 /* image input of dyk_image_prep only */,
+       DYK_F16 = 3 /* IEEE half, inference: forward kernels only (backward, weight-gradient and BatchNorm-statistics forms
+                      return DYK_ERR_UNSUPPORTED); every store saturates to +-65504, round to nearest even, NaN kept */ };
 
 /* activation codes; the strings are the cfg `activation=` values (models.py:51-64) */
 enum {

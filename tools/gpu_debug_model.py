@@ -1,5 +1,5 @@
 """Per-layer parity dump of the HIP plan against the oracle on the GPU box.
-usage: python tools/gpu_debug_model.py <cfg-name> [fp32|bf16] [train|eval] [bwd]"""
+usage: python tools/gpu_debug_model.py <cfg-name> [fp32|bf16|fp16] [train|eval] [bwd]   (fp16: eval only)"""
 import os
 import sys
 os.environ["DYK_DEBUG_PLAN"] = "1"
@@ -16,7 +16,8 @@ from models import YOLO  # noqa: E402
 
 def tref_to_nchw(plan, t):
     es = t.esize
-    dt = torch.float32 if es == 4 else torch.bfloat16
+    # a 16-bit tensor holds the plan's compute type (bf16, or fp16 in an inference plan); fp32 islands (heads) have esize 4
+    dt = torch.float32 if es == 4 else plan.dtype
     a = plan.arenas[t.arena].tensor
     n = t.npix * t.ld
     flat = a[t.off:t.off + n * es].view(dt)[:n] if False else a[t.off:t.off + (n - (t.ld - t.C)) * es].view(dt)
