@@ -61,3 +61,29 @@ def tref_to_nchw(plan, t):
     flat = a[t.off:t.off + (n - (t.ld - t.C)) * es].view(dt)
     v = torch.as_strided(flat, (t.B, t.H, t.W, t.C), (t.H * t.W * t.ld, t.W * t.ld, t.ld, 1))
     return v.float().permute(0, 3, 1, 2).contiguous().cpu()
+
+
+_LOSS_FAMILY_CACHE = {}
+
+
+def loss_family(kind, seed):
+    """oracle.loss.loss_input_family(kind, seed) with everything a loss test needs, computed once per process and shared (do not
+    modify): dict(cfg, nc, hyp, gr, v4, p, targets, anchor_vecs, r64, r32) -- r64 / r32 = oracle.loss.loss_reference in float64 /
+    float32, the reference and the yardstick of tests/test_loss_reference.py and tests/test_gpu_loss_elements.py"""
+    import sys
+    import torch
+    if GOLDEN not in sys.path:
+        sys.path.insert(0, GOLDEN)
+    import cases
+    from oracle import loss as oloss
+    key = (kind, seed)
+    if key not in _LOSS_FAMILY_CACHE:
+        cfg, nc, over, gr, p, targets = oloss.loss_input_family(kind, seed)
+        anchors, strides, v4 = cases.head_geometry(cfg)
+        av = [torch.tensor(a, dtype=torch.float32) / s for a, s in zip(anchors, strides)]
+        hyp = dict(cases.load_hyp("hyp.scratch.4" if v4 else "hyp.scratch"), **over)
+        f = dict(cfg=cfg, nc=nc, hyp=hyp, gr=gr, v4=v4, p=p, targets=targets, anchor_vecs=av)
+        f["r64"] = oloss.loss_reference(p, targets, av, hyp, nc, gr, v4, dtype=torch.float64)
+        f["r32"] = oloss.loss_reference(p, targets, av, hyp, nc, gr, v4, dtype=torch.float32)
+        _LOSS_FAMILY_CACHE[key] = f
+    return _LOSS_FAMILY_CACHE[key]
