@@ -177,6 +177,16 @@ class DykOptimDesc(ctypes.Structure):
                 ("zero_grad", _i32)]
 
 
+class DykGradGuardRec(ctypes.Structure):
+    _fields_ = [("sumsq", ctypes.c_double), ("norm", _f32), ("coef", _f32), ("nonfinite", ctypes.c_uint32), ("skip", _i32),
+                ("applied", _i32), ("skipped", _i32), ("bc1", _f32), ("bc2_sqrt", _f32)]
+
+
+class DykGradStatsDesc(ctypes.Structure):
+    _fields_ = [("g", _vp), ("mask", _vp), ("ws", _vp), ("rec", _vp), ("n", _i64), ("ws_bytes", _i64), ("grad_scale", _f32),
+                ("max_norm", _f32), ("beta1", _f32), ("beta2", _f32), ("skip_nonfinite", _i32), ("_pad", _i32)]
+
+
 class DykEmaDesc(ctypes.Structure):
     _fields_ = [("src", _vp * EMA_MAX_REGIONS), ("dst", _vp * EMA_MAX_REGIONS), ("n", _i64 * EMA_MAX_REGIONS),
                 ("nregions", _i32), ("d", _f32), ("omd", _f32)]
@@ -257,6 +267,11 @@ SIGNATURES = {
     "dyk_nms": (_i32, [_P(DykNmsDesc), _vp]),
     "dyk_adam_step": (_i32, [_P(DykOptimDesc), _vp]),
     "dyk_sgd_step": (_i32, [_P(DykOptimDesc), _vp]),
+    "dyk_grad_stats_ws_bytes": (_i64, [_i64]),
+    "dyk_grad_stats": (_i32, [_P(DykGradStatsDesc), _vp]),
+    "dyk_adam_step_guarded": (_i32, [_P(DykOptimDesc), _vp, _vp]),
+    "dyk_sgd_step_guarded": (_i32, [_P(DykOptimDesc), _vp, _vp]),
+    "dyk_grad_scale_by_rec": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "dyk_ema_update": (_i32, [_P(DykEmaDesc), _vp]),
     "dyk_run_commands_timed": (_i32, [_P(DykCommand), _i32, _vp, _P(_f32)]),
     "dyk_loss_scale_grads": (_i32, [_vp, _i64, _i32, _vp, _vp]),

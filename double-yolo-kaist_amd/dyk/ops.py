@@ -346,3 +346,55 @@ def bn_finalize(stats, count, gamma, beta, running_mean, running_var, momentum=0
     d.C, d.count, d.momentum, d.eps = C, count, momentum, eps
     call("dyk_bn_finalize", d)
     return scale, shift, mean, rstd
+
+
+# --------------------------------------------------------------------------- gradient guard (csrc/optim_guard.hip)
+GRAD_REC_BYTES = ctypes.sizeof(_l.DykGradGuardRec)
+
+
+def grad_guard_record(device):
+    """a zeroed DykGradGuardRec in device memory (bytes); the caller keeps it across steps"""
+    return torch.zeros(GRAD_REC_BYTES, dtype=torch.uint8, device=device)
+
+
+def grad_stats_workspace(n, device):
+    return torch.empty(int(load().dyk_grad_stats_ws_bytes(n)), dtype=torch.uint8, device=device)
+
+
+def grad_record_from_bytes(host_bytes):
+    """DykGradGuardRec (ctypes) from 40 bytes of a host copy of the record"""
+    return _l.DykGradGuardRec.from_buffer_copy(bytes(host_bytes))
+
+
+def read_grad_record(rec):
+    """the record as a ctypes struct; copies to the host (synchronises)"""
+    return grad_record_from_bytes(rec.cpu().numpy().tobytes())
+
+
+def grad_stats(g, rec, ws, *, mask=None, grad_scale=1.0, max_norm=0.0, beta1=0.0, beta2=0.0, skip_nonfinite=False, n=None):
+    """norm / non-finite count / clip coefficient / skip decision of the flat fp32 gradient `g` into the record `rec`"""
+    _require_cuda(g, rec, ws, mask)
+    d = _l.DykGradStatsDesc()
+    d.g, d.mask, d.ws, d.rec = g.data_ptr(), (mask.data_ptr() if mask is not None else None), \
+        (ws.data_ptr() if ws is not None else None), (rec.data_ptr() if rec is not None else None)
+    d.n = g.numel() if n is None else n
+    d.ws_bytes = ws.numel() * ws.element_size() if ws is not None else 0
+    d.grad_scale, d.max_norm, d.beta1, d.beta2 = grad_scale, max_norm, beta1, beta2
+    d.skip_nonfinite = 1 if skip_nonfinite else 0
+    call("dyk_grad_stats", d)
+
+
+def adam_step_guarded(desc, rec):
+    """dyk_adam_step on the DykOptimDesc `desc`, with skip / clip coefficient / bias corrections from the record"""
+    check(load().dyk_adam_step_guarded(ctypes.byref(desc), _ptr(rec), _stream()), "dyk_adam_step_guarded")
+
+
+def sgd_step_guarded(desc, rec):
+    check(load().dyk_sgd_step_guarded(ctypes.byref(desc), _ptr(rec), _stream()), "dyk_sgd_step_guarded")
+
+
+def grad_scale_by_rec(g, rec, mask=None, n=None):
+    """g *= rec.coef on live elements (nothing is written when coef == 1)"""
+    _require_cuda(g, rec, mask)
+    check(load().dyk_grad_scale_by_rec(_ptr(g), _ptr(mask), g.numel() if n is None else n, _ptr(rec), _stream()),
+          "dyk_grad_scale_by_rec")

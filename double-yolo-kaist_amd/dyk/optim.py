@@ -5,6 +5,10 @@ rule, same constructor arguments, `step()` / `zero_grad()` / `param_groups[0]['l
 `state_dict()` / `load_state_dict()` in torch.optim's own per-parameter format (the reference checkpoint stores
 `optimizer.state_dict()`, train.py:229), and -- like `pg = [p for p in model.parameters() if p.requires_grad]`
 (train.py:84) -- no update of parameters frozen with `requires_grad_(False)` (`--freeze-layers`, train.py:77-82).
+
+Opt-in protection (`max_grad_norm=`, `skip_nonfinite=`): what the reference harness gets from amp.GradScaler
+(train_utils/kaist_train_eval_utils.py:44,103-108) and torch.nn.utils.clip_grad_norm_, decided on the device from one
+reduction over the flat gradient buffer (csrc/optim_guard.hip) -- no per-tensor kernels, no host synchronisation.
 """
 import ctypes
 
@@ -17,7 +21,16 @@ from .lib import check, load
 class _FusedBase(torch.optim.Optimizer):
     _state_names = ()            # torch.optim state entries that map onto the flat buffers (m, v)
 
-    def __init__(self, model, defaults):
+    def __init__(self, model, defaults, max_grad_norm=None, skip_nonfinite=False):
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (0.0 < max_grad_norm < float("inf")):
+                raise ValueError("max_grad_norm must be a positive finite number or None, got %r" % (max_grad_norm,))
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guarded = self.skip_nonfinite or max_grad_norm is not None
+        self._rec = self._stats_ws = None            # device record / workspace of the guarded mode (never allocated otherwise)
+        self._stats_ring, self._stats_pending, self._stats_last = None, [], None
         self.model = model
         params = [p for p in model.parameters() if p.requires_grad]
         if not params:
@@ -178,6 +191,81 @@ class _FusedBase(torch.optim.Optimizer):
         self._wc_complete = bf is not None and (mask is None or bf["version"] == st.version_key())
         return d, bf
 
+    # ------------------------------------------------------------------ guarded mode (max_grad_norm / skip_nonfinite)
+    _REC_APPLIED = 6             # int32 index of DykGradGuardRec.applied (include/dyk_hip.h)
+
+    def _guard_record(self, st):
+        if self._rec is None or self._rec.device != st.P.device:
+            from . import ops
+            if self._rec is not None:        # the model moved: carry the applied count over
+                self.grad_stats(wait=True)
+            self._rec = ops.grad_guard_record(st.P.device)
+            self._stats_ws = ops.grad_stats_workspace(st.total, st.P.device)
+            self._stats_ring = [torch.zeros(8, ops.GRAD_REC_BYTES, dtype=torch.uint8).pin_memory(), 0]
+            if self._t:                      # a checkpoint was loaded before the first step
+                self._rec.view(torch.int32)[self._REC_APPLIED] = self._t
+            self._fresh = True
+        return self._rec
+
+    def _guarded_step(self, st, d, bf, step_fn, name, beta1, beta2):
+        """dyk_grad_stats over the whole G on the caller's stream (behind everything enqueued so far: the backward, a
+        data-parallel all-reduce), the record's asynchronous copy to pinned memory, then the guarded step -- one launch or the
+        two ranges of _launch, both reading the same record.  With data-parallel buckets the norm needs all of G: the caller's
+        stream waits for every bucket first and the bucket-wise overlap is given up (every rank holds the same G afterwards
+        and reaches the same decision without a further collective)."""
+        from . import ops
+        buckets, self._buckets = self._buckets, None
+        if buckets is not None:
+            for w, _, _ in buckets:
+                w.wait()
+        rec = self._guard_record(st)
+        mask = self._mask                    # (_desc has refreshed it)
+        if self.skip_nonfinite:
+            # a skipped step writes no bf16 copy at all: the cast may be left out only if the copy was current before the step
+            self._wc_complete = bf is not None and bf["version"] == st.version_key()
+        ops.grad_stats(st.G, rec, self._stats_ws, mask=mask, grad_scale=d.grad_scale, max_norm=self.max_grad_norm or 0.0,
+                       beta1=beta1, beta2=beta2, skip_nonfinite=self.skip_nonfinite)
+        self._publish_stats(rec)
+        early_start, self.early_start = self.early_start, False     # (the side stream must wait for the statistics)
+        try:
+            rp = ctypes.c_void_p(rec.data_ptr())
+            self._launch(lambda dref, stream: step_fn(dref, rp, stream), name, d, bf)
+        finally:
+            self.early_start = early_start
+
+    def _publish_stats(self, rec):
+        ring, pend = self._stats_ring, self._stats_pending
+        self._poll_stats()
+        if len(pend) >= ring[0].shape[0]:        # the host runs a whole ring ahead of the device: wait for the oldest copy
+            pend[0][1].synchronize()
+            self._poll_stats()
+        host = ring[0][ring[1] % ring[0].shape[0]]
+        ring[1] += 1
+        host.copy_(rec, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        pend.append((host, ev))
+
+    def _poll_stats(self):
+        from . import ops
+        pend = self._stats_pending
+        while pend and pend[0][1].query():
+            host, _ = pend.pop(0)
+            r = ops.grad_record_from_bytes(host.numpy().tobytes())
+            self._stats_last = dict(norm=float(r.norm), clip_coef=float(r.coef), nonfinite=int(r.nonfinite),
+                                    applied_steps=int(r.applied), skipped_steps=int(r.skipped))
+            self._t = int(r.applied)
+
+    def grad_stats(self, wait=False):
+        """{norm, clip_coef, nonfinite, applied_steps, skipped_steps} of the newest guarded step whose record has reached the
+        host (norm is that of grad * grad_scale over the trainable parameters), or None.  wait=False never synchronises: the
+        answer may be a step or two old.  wait=True waits for the copy behind the last step()."""
+        if wait and self._stats_pending:
+            self._stats_pending[-1][1].synchronize()
+        if self._stats_pending:
+            self._poll_stats()
+        return None if self._stats_last is None else dict(self._stats_last)
+
     def _check_loss_flag(self):
         """the reference raises IndexError inside compute_loss when a target lies on the right / bottom image edge
         (grid index == grid size: build_utils/utils.py:370 with :248); the HIP loss records that in a device flag
@@ -214,6 +302,8 @@ class _FusedBase(torch.optim.Optimizer):
             self.state[p] = s
 
     def state_dict(self):
+        if self._guarded and self._rec is not None:
+            self.grad_stats(wait=True)       # step = steps actually applied (a skipped step does not advance Adam's t)
         self._export_state()
         return super().state_dict()
 
@@ -239,6 +329,9 @@ class _FusedBase(torch.optim.Optimizer):
         # torch.optim.SGD keeps only 'momentum_buffer' (no 'step'): a checkpoint that carries buffers is past its first
         # step -- with _t = 0 the next step would take the first-step branch (m = g) and drop the loaded momentum
         self._t = steps.pop() if steps else (1 if loaded else 0)
+        if self._rec is not None:
+            self.grad_stats(wait=True)       # (copies of earlier steps must not overwrite _t afterwards)
+            self._rec.view(torch.int32)[self._REC_APPLIED] = self._t
         self.state.clear()               # the flat buffers are the state; views are rebuilt on demand
         self._fresh = True               # (the copies above ran on the caller's stream)
 
@@ -246,14 +339,17 @@ class _FusedBase(torch.optim.Optimizer):
 class FusedAdam(_FusedBase):
     _state_names = ("exp_avg", "exp_avg_sq")
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 skip_nonfinite=False):
+        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm, skip_nonfinite)
 
     @torch.no_grad()
     def step(self, closure=None):
         st = self._store()
         self._check_loss_flag()
         st.attach_grads()
+        if self._guarded:
+            return self._step_guarded(st)
         self._t += 1
         d, bf = self._desc(st)
         g = self.param_groups[0]
@@ -261,22 +357,74 @@ class FusedAdam(_FusedBase):
         self._launch(load().dyk_adam_step, "dyk_adam_step", d, bf)
         self._finish(st, bf)
 
+    def _step_guarded(self, st):
+        d, bf = self._desc(st)
+        g = self.param_groups[0]
+        d.beta1, d.beta2, d.eps, d.step = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), 0
+        self._guarded_step(st, d, bf, load().dyk_adam_step_guarded, "dyk_adam_step_guarded", d.beta1, d.beta2)
+        self._finish(st, bf)
+
 
 class FusedSGD(_FusedBase):
     _state_names = ("momentum_buffer",)
 
-    def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=0.0, nesterov=True):
+    def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=0.0, nesterov=True, max_grad_norm=None,
+                 skip_nonfinite=False):
         if not nesterov:
             raise NotImplementedError("the reference only uses nesterov=True (train.py:88-89)")
-        super().__init__(model, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=True, dampening=0))
+        super().__init__(model, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=True, dampening=0),
+                         max_grad_norm, skip_nonfinite)
 
     @torch.no_grad()
     def step(self, closure=None):
         st = self._store()
         self._check_loss_flag()
         st.attach_grads()
+        if self._guarded:
+            return self._step_guarded(st)
         self._t += 1
         d, bf = self._desc(st)
         d.beta1, d.step = float(self.param_groups[0]["momentum"]), self._t
         self._launch(load().dyk_sgd_step, "dyk_sgd_step", d, bf)
         self._finish(st, bf)
+
+    def _step_guarded(self, st):
+        d, bf = self._desc(st)
+        d.beta1, d.step = float(self.param_groups[0]["momentum"]), 0
+        self._guarded_step(st, d, bf, load().dyk_sgd_step_guarded, "dyk_sgd_step_guarded", 0.0, 0.0)
+        self._finish(st, bf)
+
+
+def clip_grad_norm_(model, max_norm, norm_type=2.0):
+    """torch.nn.utils.clip_grad_norm_ for users of stock torch.optim on the gradient views of a dyk model: one reduction over
+    the flat gradient buffer (dyk_grad_stats) and one scaling launch (dyk_grad_scale_by_rec, which stores nothing when the
+    norm is within `max_norm`) instead of per-tensor kernels over some 600 views.  Same coefficient as torch,
+    max_norm / (norm + 1e-6) clamped to 1, over the trainable parameters; a non-finite norm scales the gradients by it, as
+    with error_if_nonfinite=False.  Returns the norm before clipping as a 0-dim tensor on the device (no synchronisation)."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError("dyk.optim.clip_grad_norm_ computes the 2-norm only (norm_type=%r)" % (norm_type,))
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:               # (the kernel reads max_norm <= 0 as "no clipping")
+        raise ValueError("max_norm must be positive, got %r" % (max_norm,))
+    from . import ops
+    m = model.module if hasattr(model, "module") and not hasattr(model, "engine") else model
+    st = m.engine.store
+    if st.P is None:
+        raise L.DykError("run one forward and backward pass before clip_grad_norm_()")
+    st.attach_grads()
+    state = m.__dict__.get("_dyk_clip")
+    key = (st.frozen_key(), st.P.device)
+    if state is None or state["key"] != key:
+        mask = None
+        if key[0]:
+            mask = torch.zeros(st.total, dtype=torch.uint8)
+            for e in st.entries:
+                if e.param.requires_grad:
+                    mask[e.offset:e.offset + e.numel] = 1
+            mask = mask.to(st.P.device)
+        state = m.__dict__["_dyk_clip"] = dict(key=key, mask=mask, rec=ops.grad_guard_record(st.P.device),
+                                               ws=ops.grad_stats_workspace(st.total, st.P.device))
+    rec, mask = state["rec"], state["mask"]
+    ops.grad_stats(st.G, rec, state["ws"], mask=mask, max_norm=max_norm)
+    ops.grad_scale_by_rec(st.G, rec, mask=mask)
+    return rec[8:12].view(torch.float32)[0].clone()

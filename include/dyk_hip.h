@@ -770,6 +770,65 @@ int dyk_adam_step(const DykOptimDesc* desc, void* stream);
 int dyk_sgd_step(const DykOptimDesc* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Non-finite guard and gradient clipping of the fused optimizers, decided on the device (replaces what the reference
+ * harness gets from amp.GradScaler -- scaler.step() skipping a step whose gradients hold inf / NaN,
+ * train_utils/kaist_train_eval_utils.py:44,103-108 -- and torch.nn.utils.clip_grad_norm_ over the gradient views, without
+ * the per-tensor kernels and without the host synchronisation of `found_inf.item()`).
+ *
+ * dyk_grad_stats : two launches on `stream` over the flat gradient buffer g[0..n):
+ *   partials : grid = min(ceil(n/4 / 256), 1024) blocks of 256 threads (a function of n only).  Every live element
+ *              (mask == NULL, or the 4 mask bytes of its 16-byte vector not all 0) is taken as x = fl32(g * grad_scale), the
+ *              value the update consumes; !(|x| <= FLT_MAX) counts as non-finite; x*x (exact in fp64) is added in fp64 per
+ *              thread in grid-stride order, then over the 64 lanes (l += l+32, l+16, ... l+1), then over the 4 waves in
+ *              order; one {sumsq, nonfinite} per block goes to `ws` (dyk_grad_stats_ws_bytes(n) bytes, 16-byte aligned)
+ *   finalize : one workgroup adds the block partials in block-index order in fp64 and one lane writes the record:
+ *              norm = fl32(sqrt(sumsq));  c = max_norm / (norm + 1e-6f) in fp32;
+ *              coef = max_norm > 0 ? (c > 1 ? 1 : c) : 1      (torch's clip_grad_norm_; a NaN norm gives a NaN coef, as
+ *                                                              with error_if_nonfinite=False)
+ *              skip = skip_nonfinite && nonfinite > 0
+ *              !skip: applied += 1, bc1 = fl32(1 - beta1^applied), bc2_sqrt = fl32(sqrt(1 - beta2^applied)), both formed
+ *              in double as dyk_adam_step forms them from `step`;  skip: skipped += 1 (bc1, bc2_sqrt keep their values)
+ *   The record lives in device memory owned by the caller and is kept across steps (applied / skipped are read and
+ *   written); zero it once.  No atomics, no in-launch hand-off: the kernel boundary orders partials before finalize.
+ * dyk_adam_step_guarded / dyk_sgd_step_guarded : dyk_adam_step / dyk_sgd_step with the decision taken from the record:
+ *   rec->skip != 0 : g is cleared when zero_grad is set; p, m, v, wc keep their bits
+ *   otherwise      : the same statements with grad_scale := fl32(desc.grad_scale * rec->coef), the bias corrections
+ *                    rec->bc1 / rec->bc2_sqrt instead of those of desc.step (which is ignored), and SGD's first-step rule
+ *                    (m = g') when rec->applied == 1.  Same contracts as DykOptimDesc above; the desc may name a sub-range.
+ * dyk_grad_scale_by_rec : g[i] = fl32(g[i] * rec->coef) on live elements; nothing is stored when rec->coef == 1.0f.
+ * n a positive multiple of 4; g 16-byte, ws 16-byte, rec 8-byte, mask 4-byte aligned; otherwise (or with a NULL g / ws / rec
+ * or ws_bytes < dyk_grad_stats_ws_bytes(n)) DYK_ERR_ARG before any launch.
+ * ---------------------------------------------------------------------------------- */
+typedef struct DykGradGuardRec {
+    double sumsq;          /* sum of x*x over the live elements */
+    float norm;            /* fl32(sqrt(sumsq)) */
+    float coef;            /* clip coefficient (1 when max_norm <= 0) */
+    uint32_t nonfinite;    /* live elements that are inf / NaN (saturates at 2^32 - 1) */
+    int32_t skip;          /* 1: the step that follows leaves p, m, v, wc alone */
+    int32_t applied;       /* steps taken so far (Adam's t) */
+    int32_t skipped;       /* steps skipped so far */
+    float bc1, bc2_sqrt;   /* bias corrections at t = applied */
+} DykGradGuardRec;
+typedef struct DykGradStatsDesc {
+    const float* g;
+    const uint8_t* mask;   /* NULL or one byte per element, 0 = frozen (not counted, not summed) */
+    void* ws;
+    DykGradGuardRec* rec;
+    int64_t n;
+    int64_t ws_bytes;
+    float grad_scale;
+    float max_norm;        /* <= 0: no clipping (coef = 1) */
+    float beta1, beta2;    /* for bc1 / bc2_sqrt (SGD: unused by the step, any value in [0, 1)) */
+    int32_t skip_nonfinite;
+    int32_t _pad;
+} DykGradStatsDesc;
+int64_t dyk_grad_stats_ws_bytes(int64_t n);
+int dyk_grad_stats(const DykGradStatsDesc* desc, void* stream);
+int dyk_adam_step_guarded(const DykOptimDesc* desc, const DykGradGuardRec* rec, void* stream);
+int dyk_sgd_step_guarded(const DykOptimDesc* desc, const DykGradGuardRec* rec, void* stream);
+int dyk_grad_scale_by_rec(float* g, const uint8_t* mask, int64_t n, const DykGradGuardRec* rec, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Exponential moving average of the flat buffers (replaces the per-entry loop of ModelEMA.update, reference
  * build_utils/torch_utils.py:108-120: `v *= d; v += (1. - d) * msd[k]` over every floating state_dict entry).
  * One launch for up to DYK_EMA_MAX_REGIONS regions (the parameter store P and the running statistics R):
