@@ -1,5 +1,6 @@
-"""Host side of the loss / target-assignment / NMS kernels (dyk_yolo_loss, dyk_build_targets, dyk_nms)."""
+"""Host side of the loss / target-assignment / NMS kernels (dyk_yolo_loss, dyk_build_targets, dyk_nms, dyk_nms_ex)."""
 import ctypes
+import os
 
 import torch
 
@@ -187,8 +188,15 @@ def compute_loss(p, targets, model):
 
 
 def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=True, classes=None, agnostic=False,
-                        max_num=100, return_rows=False):
-    """reference build_utils/utils.py:387-464 -> list (per image) of [n,6] tensors or None."""
+                        max_num=100, return_rows=False, merge=None):
+    """reference build_utils/utils.py:387-464 -> list (per image) of [n,6] tensors or None.
+
+    merge: the reference's `merge` setting (utils.py:398, False as shipped; :450-454): every kept box becomes the
+    score-weighted mean of all candidates that overlap it by more than iou_thres, in images with 1 < n < 3000 candidates.
+    None reads DYK_NMS_MERGE from the environment (unset or 0 = off), so an unchanged evaluate.py can switch it on;
+    True / False override the environment."""
+    if merge is None:
+        merge = os.environ.get("DYK_NMS_MERGE", "0") not in ("", "0")
     _require_cuda(prediction, "non_max_suppression")
     pred = prediction.detach().float().contiguous()
     B, N, no = pred.shape
@@ -209,7 +217,10 @@ def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=T
     d.n_classes = len(cl)
     for i, c in enumerate(cl[:16]):
         d.classes[i] = int(c)
-    check(lib.dyk_nms(ctypes.byref(d), _stream()), "dyk_nms")
+    if merge:
+        check(lib.dyk_nms_ex(ctypes.byref(d), L.NMS_MERGE, _stream()), "dyk_nms_ex")
+    else:
+        check(lib.dyk_nms(ctypes.byref(d), _stream()), "dyk_nms")
     cnt = counts.cpu().tolist()                    # the one host sync of the eval step
     res = [out[b, :n] if n else None for b, n in enumerate(cnt)]
     if return_rows:

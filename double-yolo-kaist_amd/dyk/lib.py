@@ -17,6 +17,7 @@ EW_ACCUM = 1
 EW_SKIP = 2
 MAX_TAPS = 25
 SE_POOL_SPLITS = 16        # DYK_SE_POOL_SPLITS (include/dyk_hip.h): partial-sum planes of the pixel-split SE pool
+NMS_MERGE = 1              # DYK_NMS_MERGE (include/dyk_hip.h): dyk_nms_ex flag, the reference's merge-NMS stage
 EMA_MAX_REGIONS = 4        # DYK_EMA_MAX_REGIONS (include/dyk_hip.h): regions of one dyk_ema_update launch
 
 # op codes of DykCommand (include/dyk_hip.h)
@@ -265,6 +266,7 @@ SIGNATURES = {
     "dyk_yolo_loss": (_i32, [_P(DykLossDesc), _P(DykTargetsDesc), _vp]),
     "dyk_nms_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "dyk_nms": (_i32, [_P(DykNmsDesc), _vp]),
+    "dyk_nms_ex": (_i32, [_P(DykNmsDesc), _i32, _vp]),
     "dyk_adam_step": (_i32, [_P(DykOptimDesc), _vp]),
     "dyk_sgd_step": (_i32, [_P(DykOptimDesc), _vp]),
     "dyk_grad_stats_ws_bytes": (_i64, [_i64]),

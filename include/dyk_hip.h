@@ -724,6 +724,20 @@ int dyk_loss_scale_grads3(float* dp, int64_t n, int32_t no, const float* gbox, c
  * suppression of IoU > iou_thres in stable descending score order, first max_num kept.  The
  * reference's 10 s wall-clock bail-out (:461-462) is deliberately not reproduced.
  * ws: B * ws_per_image bytes, ws_per_image >= dyk_nms_workspace_bytes(N, no, multi_label).
+ *
+ * dyk_nms_ex(desc, flags, stream): dyk_nms(d, s) == dyk_nms_ex(d, 0, s); unknown flag bits -> DYK_ERR_ARG.
+ * DYK_NMS_MERGE: the reference's merge-NMS stage (utils.py:398 `merge`, :450-454; False as shipped), in the same
+ * launch.  Per image with candidate count n (after every filter; in multi_label mode one row can give several) and
+ * only when 1 < n < 3000 (:450, both strict -- otherwise the output is the plain one bit for bit):
+ *   member(k, j) = box_iou(boxes[i[k]], boxes[j]) > iou_thres  (:452, box_iou :141-163: inter / (area_k + area_j -
+ *                  inter) in fp32 on the class-offset boxes of :447 as rounded, strict), over ALL n candidates -- the
+ *                  suppressed ones, the kept box itself and survivors cut off by max_num;
+ *   out[b][k][0..4) = sum_j member * conf_j * xyxy_j / sum_j member * conf_j  (:453-454) over the un-offset corners
+ *                  of the original candidates (the right-hand side never sees a merged box).
+ * conf, cls, order, counts and out_rows are those of the plain call.  Each coordinate lies within
+ * 2^-23 * max(|exact|, 1) of the exact weighted mean of the fp32 inputs (fp64 accumulation, one rounding to fp32;
+ * the reference's torch.mm sums in fp32) and is bit-identical from run to run.  The workspace size does not change.
+ * The reference's try/except around the merge and its print are not reproduced.
  * ---------------------------------------------------------------------------------- */
 typedef struct DykNmsDesc {
     const float* pred;
@@ -740,6 +754,8 @@ typedef struct DykNmsDesc {
 } DykNmsDesc;
 int64_t dyk_nms_workspace_bytes(int32_t N, int32_t no, int32_t multi_label);
 int dyk_nms(const DykNmsDesc* desc, void* stream);
+#define DYK_NMS_MERGE 1
+int dyk_nms_ex(const DykNmsDesc* desc, int32_t flags, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Fused optimizer step over the flat parameter store (replaces the per-tensor torch.optim.Adam /
