@@ -114,135 +114,12 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DykDwDesc d, int CVB) {
     }
 }
 
-// Stride-1 fast path of the kernel above: a thread produces XT = 4 neighbouring pixels of a row for its 8 channels and
-// keeps the (4 + K - 1) source vectors of each kernel row in registers: (K + 3) / 4 loads per output and row instead of
-// K (2 x fewer for 3x3, 2.5 x fewer for 5x5), weights of a kernel row read once per strip.
-template <typename T, int K, bool GRAD>
-__global__ __launch_bounds__(256) void dwconv_strip_kernel(DykDwDesc d, int CVB) {
-    constexpr int EPV = ElemTraits<T>::EPV;
-    constexpr int XT = 4, NS = XT + K - 1;
-    __shared__ float red[256 * 2 * 8];
-    const int PY = 256 / CVB;
-    const int tx = threadIdx.x % CVB, ty = threadIdx.x / CVB;
-    const int cv = blockIdx.x * CVB + tx;
-    const int c = cv * EPV;
-    const bool active = c < d.C;
-    const T* __restrict__ x = GRAD ? (const T*)d.y : (const T*)d.x;     // tensor read
-    T* __restrict__ y = GRAD ? (T*)d.x : (T*)d.y;                       // tensor written
-    const int ld_src = GRAD ? d.ldy : d.ldx, ld_dst = GRAD ? d.ldx : d.ldy;
-    const int pad = d.pad;
-    const int H = d.Hi, W = d.Wi;                  // stride 1: source and destination extents differ only by k - 1 - 2 pad
-    const int Hout = GRAD ? d.Hi : d.Ho, Wout = GRAD ? d.Wi : d.Wo;
-    const int Hsrc = GRAD ? d.Ho : d.Hi, Wsrc = GRAD ? d.Wo : d.Wi;
-    (void)H; (void)W;
-    const bool accum = d.flags & DYK_EW_ACCUM;
-    const bool stats = (!GRAD) && d.stats != nullptr;
-    float s1[EPV], s2[EPV];
-#pragma unroll
-    for (int j = 0; j < EPV; ++j) s1[j] = s2[j] = 0.f;
-    if (active) {
-        const int nrows = d.B * Hout;
-        for (int row = blockIdx.y; row < nrows; row += gridDim.y) {
-            const int b = row / Hout, yo = row - b * Hout;
-            for (int xo0 = ty * XT; xo0 < Wout; xo0 += PY * XT) {
-                float acc[XT][EPV];
-#pragma unroll
-                for (int o = 0; o < XT; ++o)
-#pragma unroll
-                    for (int j = 0; j < EPV; ++j) acc[o][j] = 0.f;
-                // source column of strip slot 0:  forward xs = xo + kw - pad ; gradient xs = xo + pad - kw
-                const int xbase = GRAD ? xo0 + pad - (K - 1) : xo0 - pad;
-#pragma unroll
-                for (int kh = 0; kh < K; ++kh) {
-                    const int ys = GRAD ? yo + pad - kh : yo + kh - pad;
-                    if (ys < 0 || ys >= Hsrc) continue;
-                    float wv[K][EPV];
-#pragma unroll
-                    for (int kw = 0; kw < K; ++kw) {
-                        const float* wp = d.w + (long)(kh * K + kw) * d.C + c;
-                        const float4 w0 = *(const float4*)wp;
-                        wv[kw][0] = w0.x; wv[kw][1] = w0.y; wv[kw][2] = w0.z; wv[kw][3] = w0.w;
-                        if (EPV == 8) {
-                            const float4 w1 = *(const float4*)(wp + 4);
-                            wv[kw][4] = w1.x; wv[kw][5] = w1.y; wv[kw][6] = w1.z; wv[kw][7] = w1.w;
-                        }
-                    }
-                    const T* srow = x + ((long)b * Hsrc + ys) * Wsrc * ld_src + c;
-                    // the NS source vectors of the row: unconditional loads from clamped columns, zeroed afterwards -- a
-                    // branch around each load made hipcc wait for every one of them on the spot (5x5: 600 GB/s)
-                    uint4 raw[NS];
-                    // (5x5: keep the batches of different kernel rows apart -- hoisted together they need 256 VGPRs, one
-                    // wave per SIMD; one row's eight loads in flight at 2-3 waves per SIMD is the better trade)
-                    if (K >= 5) asm volatile("" ::: "memory");
-#pragma unroll
-                    for (int sl = 0; sl < NS; ++sl) {
-                        const int xs = xbase + sl;
-                        const int xc = xs < 0 ? 0 : (xs >= Wsrc ? Wsrc - 1 : xs);
-                        raw[sl] = *(const uint4*)(srow + (long)xc * ld_src);
-                    }
-#pragma unroll
-                    for (int sl = 0; sl < NS; ++sl) {
-                        const int xs = xbase + sl;
-                        const bool in = xs >= 0 && xs < Wsrc;
-                        float xv[EPV];
-                        vec_unpack<T>(raw[sl], xv);
-#pragma unroll
-                        for (int j = 0; j < EPV; ++j) xv[j] = in ? xv[j] : 0.f;
-#pragma unroll
-                        for (int o = 0; o < XT; ++o) {
-                            const int kw = GRAD ? o + (K - 1) - sl : sl - o;       // compile-time after unrolling
-                            if (kw < 0 || kw >= K) continue;
-#pragma unroll
-                            for (int j = 0; j < EPV; ++j) acc[o][j] += xv[j] * wv[kw][j];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int o = 0; o < XT; ++o) {
-                    const int xo = xo0 + o;
-                    if (xo >= Wout) break;
-                    if (stats) {
-#pragma unroll
-                        for (int j = 0; j < EPV; ++j) { s1[j] += acc[o][j]; s2[j] += acc[o][j] * acc[o][j]; }
-                    }
-                    T* yp = y + ((long)row * Wout + xo) * ld_dst + c;
-                    if (accum) {
-                        float old[EPV];
-                        vec_unpack<T>(*(const uint4*)yp, old);
-#pragma unroll
-                        for (int j = 0; j < EPV; ++j) acc[o][j] += old[j];
-                    }
-                    *(uint4*)yp = vec_pack<T>(acc[o]);
-                }
-            }
-        }
-    }
-    if (stats) {
-        float* mine = red + threadIdx.x * 16;
-#pragma unroll
-        for (int j = 0; j < EPV; ++j) { mine[j] = s1[j]; mine[8 + j] = s2[j]; }
-        __syncthreads();
-        if (ty == 0 && active) {
-            for (int q = 1; q < PY; ++q) {
-                const float* o = red + (q * CVB + tx) * 16;
-#pragma unroll
-                for (int j = 0; j < EPV; ++j) { s1[j] += o[j]; s2[j] += o[8 + j]; }
-            }
-            double* st = d.stats + (size_t)(blockIdx.y % (unsigned)(d.stats_slots > 0 ? d.stats_slots : 1)) * 2 * d.C;
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) {
-                atomicAdd(st + c + j, (double)s1[j]);
-                atomicAdd(st + d.C + c + j, (double)s2[j]);
-            }
-        }
-    }
-}
-
 // LDS-tiled stride-1 depthwise conv (bf16; forward, and the data gradient as the same correlation with the flipped kernel
 // and pad' = K - 1 - pad).  A workgroup stages the input patch of a TH x 16 pixel output tile for CT <= 8 channel vectors
 // in LDS -- every thread issues all of its (<= 8) 16-byte loads before anything waits, ONE memory round trip per tile
-// -- and the k x k taps are then ds_read_b128s.  The register-strip kernel above re-reads the patch through L1 in K
-// dependent batches per strip (one round trip per kernel row): 1.1-1.9 TB/s on the MobileNetV3 layers, latency-bound.
+// -- and the k x k taps are then ds_read_b128s.  (Its predecessor, a register-strip kernel that re-read the patch through
+// L1 in K dependent batches per strip, ran at 1.1-1.9 TB/s on the MobileNetV3 layers, latency-bound; it was removed once no
+// shape could reach it, see launch_dw_tile.)
 // Thread = (channel vector ct, strip of XT = 4 pixels, tile row); tile [rows][cols][S = CT|1] 16-byte slots (odd slot
 // stride: <= 2-way bank conflicts, irrelevant next to the VALU work); weights [K*K][CT*8] fp32 behind the tile.
 template <int K, bool GRAD, typename T = bf16_t>
@@ -472,6 +349,12 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, i
     }
 }
 
+// Every stride-1 k = 3 | 5 16-bit problem runs here.  CT is 1..8 by construction, and the patch of every CT fits the NLD * 256
+// staging loads (IR * IC * CT vectors; RT = (256 / CT) / 4, IR = RT + K - 1, IC = 16 + K - 1):
+//   CT          1     2     3     4     5     6     7     8
+//   k = 3    1188  1224  1242  1296  1260  1296  1386  1440   of 1536
+//   k = 5    1360  1440  1500  1600  1600  1680  1820  1920   of 2048
+// and LDS stays below 64 KB (k = 3: 29.4 KB at most, k = 5: 40.5 KB).  What is left to refuse is a grid of 2^31 workgroups.
 template <int K, bool GRAD, typename T = bf16_t>
 int launch_dw_tile(const DykDwDesc* d, hipStream_t stream) {
     constexpr int TW = 16, IC = TW + K - 1, NLD = K == 5 ? 8 : 6;
@@ -490,11 +373,10 @@ int launch_dw_tile(const DykDwDesc* d, hipStream_t stream) {
                        m_ct, tiles_x, tiles_y);
     return DYK_OK;
 }
-inline bool dw_tile_on() { return true; }
 
 // Stride-2 fast path (MobileNet down-sampling layers): K and the stride are compile-time, so the taps of a pixel are a
-// fixed, unrolled set whose loads are issued together -- clamped coordinates, values zeroed afterwards (the generic kernel
-// above walks runtime loops with a branch around every load: one memory round trip per tap).
+// fixed, unrolled set whose loads are issued together -- clamped coordinates, values zeroed afterwards (dwconv_kernel
+// walks runtime loops with a branch around every load: one memory round trip per tap).
 //   forward : y[yo, xo] = sum_{kh,kw} x[2 yo + kh - pad, 2 xo + kw - pad] w[kh, kw]              (K*K loads)
 //   gradient: dx[yi, xi] = sum over the taps of yi's / xi's parity, kh = (yi + pad) % 2 + 2 a:
 //             dy[(yi + pad - kh) / 2, (xi + pad - kw) / 2] w[kh, kw]                              (ceil(K/2)^2 loads)
@@ -759,7 +641,7 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(DykDwDesc d, int CVB)
     }
 }
 
-// LDS-tiled, PERSISTENT stride-1 depthwise weight gradient (bf16, k = 3 | 5; round 5).  The kernel above makes K passes over dy
+// LDS-tiled, PERSISTENT stride-1 depthwise weight gradient (bf16, k = 3 | 5; round 5).  dwconv_wgrad_kernel above makes K passes over dy
 // and x (grid.z = kernel row) with 12 sixteen-byte loads in flight per thread and three waves per SIMD: ~0.6 MB in flight over the
 // chip, 0.5-2 TB/s, waiting 0.64-0.74 of its cycles (tools/dw_pmc.sh).  Here a workgroup walks output tiles of TH x 16 pixels for
 // CT <= 8 channel vectors (the geometry of dwconv_tile_kernel): the x patch and the dy tile of the NEXT tile are requested into
@@ -1035,25 +917,22 @@ extern "C" int dyk_dwconv_fwd(const DykDwDesc* d, void* stream) {
     if (d->dtype == DYK_F16) {
         // the inference type: the same kernel choice as bf16, no BatchNorm statistics, no normalise-on-load (train-mode forms)
         if (d->stats || d->pre) return DYK_ERR_UNSUPPORTED;
-        if (d->stride == 1 && (d->k == 3 || d->k == 5) && dw_tile_on()) {
+        if (d->stride == 1 && (d->k == 3 || d->k == 5)) {
             const int rt = d->k == 3 ? launch_dw_tile<3, false, f16_t>(d, (hipStream_t)stream) : launch_dw_tile<5, false, f16_t>(d, (hipStream_t)stream);
-            if (rt != DYK_ERR_UNSUPPORTED) { DYK_LAUNCH_CHECK(); return rt; }
+            if (rt == DYK_OK) DYK_LAUNCH_CHECK();
+            return rt;
         }
-        if (d->stride == 1 && d->k == 3) hipLaunchKernelGGL((dwconv_strip_kernel<f16_t, 3, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-        else if (d->stride == 1 && d->k == 5) hipLaunchKernelGGL((dwconv_strip_kernel<f16_t, 5, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-        else hipLaunchKernelGGL((dwconv_kernel<f16_t, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
+        hipLaunchKernelGGL((dwconv_kernel<f16_t, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
         DYK_LAUNCH_CHECK();
         return DYK_OK;
     }
-    if (d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16 && dw_tile_on()) {
+    if (d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16) {
         const int rt = d->k == 3 ? launch_dw_tile<3, false>(d, (hipStream_t)stream) : launch_dw_tile<5, false>(d, (hipStream_t)stream);
-        if (rt != DYK_ERR_UNSUPPORTED) { DYK_LAUNCH_CHECK(); return rt; }
+        if (rt == DYK_OK) DYK_LAUNCH_CHECK();
+        return rt;
     }
     if (d->pre) return DYK_ERR_UNSUPPORTED;        // normalise + activation on load: the LDS-tiled kernel only (dyk_dwconv_tile_ok)
-    if (d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16) {
-        if (d->k == 3) hipLaunchKernelGGL((dwconv_strip_kernel<bf16_t, 3, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-        else hipLaunchKernelGGL((dwconv_strip_kernel<bf16_t, 5, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    } else if (d->dtype == DYK_BF16)      // (stride 2 forward: the generic kernel measured faster than dwconv_s2_kernel<.., false>)
+    if (d->dtype == DYK_BF16)      // (stride 2 forward: the generic kernel measured faster than dwconv_s2_kernel<.., false>)
         hipLaunchKernelGGL((dwconv_kernel<bf16_t, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
     else
         hipLaunchKernelGGL((dwconv_kernel<float, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
@@ -1064,7 +943,7 @@ extern "C" int dyk_dwconv_fwd(const DykDwDesc* d, void* stream) {
 extern "C" int dyk_dwconv_tile_ok(const DykDwDesc* d) {
     const int rc = check_dw(d);
     if (rc) return rc;
-    if (!(d->stride == 1 && (d->k == 3 || d->k == 5) && (d->dtype == DYK_BF16 || d->dtype == DYK_F16) && dw_tile_on())) return 0;
+    if (!(d->stride == 1 && (d->k == 3 || d->k == 5) && (d->dtype == DYK_BF16 || d->dtype == DYK_F16))) return 0;
     const int K = d->k, TW = 16, IC = TW + K - 1, NLD = K == 5 ? 8 : 6;
     const int CV = d->C / 8;
     const int groups = (CV + 7) / 8, CT = (CV + groups - 1) / groups;
@@ -1090,14 +969,12 @@ extern "C" int dyk_dwconv_dgrad(const DykDwDesc* d, void* stream) {
     const int epv = d->dtype == DYK_BF16 ? 8 : 4;
     int gx, gy;
     const int CVB = grid2d(d->C / epv, (long)d->B * d->Hi, &gx, &gy, 4096);
-    if (d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16 && dw_tile_on()) {
-        const int rt = d->k == 3 ? launch_dw_tile<3, true>(d, (hipStream_t)stream) : launch_dw_tile<5, true>(d, (hipStream_t)stream);
-        if (rt != DYK_ERR_UNSUPPORTED) { DYK_LAUNCH_CHECK(); return rt; }
-    }
     if (d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16) {
-        if (d->k == 3) hipLaunchKernelGGL((dwconv_strip_kernel<bf16_t, 3, true>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-        else hipLaunchKernelGGL((dwconv_strip_kernel<bf16_t, 5, true>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    } else if (d->stride == 2 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16) {
+        const int rt = d->k == 3 ? launch_dw_tile<3, true>(d, (hipStream_t)stream) : launch_dw_tile<5, true>(d, (hipStream_t)stream);
+        if (rt == DYK_OK) DYK_LAUNCH_CHECK();
+        return rt;
+    }
+    if (d->stride == 2 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16) {
         if (d->k == 3) hipLaunchKernelGGL((dwconv_s2_kernel<bf16_t, 3, true>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
         else hipLaunchKernelGGL((dwconv_s2_kernel<bf16_t, 5, true>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
     } else if (d->dtype == DYK_BF16)
