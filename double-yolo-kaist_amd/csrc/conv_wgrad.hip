@@ -120,18 +120,14 @@ __global__ __launch_bounds__(256 * KG) void conv_wgrad_kernel(const WgArgs args,
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi) {
                     const int ch = wm * WTM + mi * 16 + 4 * (i16 & 3);
-                    v4i16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)(pa + wg_off<T, BM>(r0, ch)));
-                    v4i16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)(pa + wg_off<T, BM>(r0 + 4, ch)));
-                    uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-                    fa[mi] = make_uint4(l2.x, l2.y, h2.x, h2.y);
+                    const uint2 lo = wg_tr_read4(pa + wg_off<T, BM>(r0, ch)), hi = wg_tr_read4(pa + wg_off<T, BM>(r0 + 4, ch));
+                    fa[mi] = make_uint4(lo.x, lo.y, hi.x, hi.y);
                 }
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) {
                     const int ch = wn * WTN + ni * 16 + 4 * (i16 & 3);
-                    v4i16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)(pb + wg_off<T, BN>(r0, ch)));
-                    v4i16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)(pb + wg_off<T, BN>(r0 + 4, ch)));
-                    uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-                    fb[ni] = make_uint4(l2.x, l2.y, h2.x, h2.y);
+                    const uint2 lo = wg_tr_read4(pb + wg_off<T, BN>(r0, ch)), hi = wg_tr_read4(pb + wg_off<T, BN>(r0 + 4, ch));
+                    fb[ni] = make_uint4(lo.x, lo.y, hi.x, hi.y);
                 }
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi)
@@ -163,8 +159,7 @@ __global__ __launch_bounds__(256 * KG) void conv_wgrad_kernel(const WgArgs args,
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    // bits 16.. of `tune`: ablation switches for kernel analysis (tools/gpu_probe.py wgablate), never set by the plan
-    const bool abl_noatomic = (a.tune >> 16) & 1, abl_noloop = (a.tune >> 17) & 1;
+    const bool abl_noatomic = wg_tune_abl_noatomic(a.tune), abl_noloop = wg_tune_abl_noloop(a.tune);
     const int S = abl_noloop ? 0 : (KG > 1 ? gchunk / ROWS : (p_end - p_begin + ROWS - 1) / ROWS);   // uniform over the K-groups
     {
         // ---- LDS-DMA ring; each wave instruction fills RPI consecutive pixel rows of a tile
@@ -369,18 +364,11 @@ int launch_wgrad_impl(const DykWgradDesc* d, hipStream_t stream, int* query) {
     const long Ntot = (long)d->B * d->Ho * d->Wo;
     const int tiles = dyk_div_up(d->Cout, BM) * dyk_div_up(d->Cin, BN) * d->ntaps;
     const int ksteps = dyk_div_up(Ntot, ROWS);
-    int splits = d->splits;
-    if (splits <= 0) {
-        // 4-wave workgroups: ~3 per CU; K-grouped (8-wave) workgroups occupy a CU alone (LDS) unless the tile is small
-        const int target = KG > 1 ? (lds > 80 * 1024 ? 256 : 512) : 768;
-        splits = dyk_div_up(target, tiles);
-        const int max_splits = ksteps / (8 * KG) > 0 ? ksteps / (8 * KG) : 1;   // at least 8 K steps per K-group (amortise the atomics)
-        if (splits > max_splits) splits = max_splits;
-    }
-    if (splits * KG > ksteps) splits = ksteps / KG > 0 ? ksteps / KG : 1;
-    const int chunk = dyk_div_up(ksteps, splits * KG) * ROWS * KG;      // pixels per workgroup: KG slices of whole K steps
-    if (!(d->part && d->splits > 0)) splits = dyk_div_up(Ntot, chunk);  // (plane mode with a given count: exactly that many
-                                                                         //  planes are written, trailing empty ones with zeros)
+    // 4-wave workgroups: ~3 per CU; K-grouped (8-wave) workgroups occupy a CU alone (LDS) unless the tile is small
+    const int target = KG > 1 ? (lds > 80 * 1024 ? 256 : 512) : 768;
+    // at least 8 K steps per K-group (amortise the atomics)
+    const WgSplitPlan p = wg_plan_splits(ksteps, tiles, target, 8, KG, d->splits, d->part && d->splits > 0);
+    const int splits = p.splits, chunk = p.chunk * ROWS;                // pixels per workgroup: KG slices of whole K steps
     if (query) { *query = splits; return DYK_OK; }
     static DykDeviceOnce attr_set;   // (the attribute is per DEVICE: one flag per device id; after the query path: no device there)
     auto kfn = conv_wgrad_kernel<T, BM, BN, PIPE, KG>;
@@ -396,24 +384,21 @@ int launch_wgrad_impl(const DykWgradDesc* d, hipStream_t stream, int* query) {
 
 template <typename T, int BM, int BN>
 int launch_wgrad(const DykWgradDesc* d, hipStream_t stream, int* query) {
-    // tune: low byte = LDS ring stages (2 | 3), bits 8..15 = K-groups per workgroup (1 | 2)
-    const int kg = (d->tune >> 8) & 0xff;
-    if ((d->tune & 0xff) == 3) return launch_wgrad_impl<T, BM, BN, 3, 1>(d, stream, query);
-    if (kg == 2) return launch_wgrad_impl<T, BM, BN, 2, 2>(d, stream, query);
+    if (wg_tune_stages(d->tune) == 3) return launch_wgrad_impl<T, BM, BN, 3, 1>(d, stream, query);
+    if (wg_tune_kgroups(d->tune) == 2) return launch_wgrad_impl<T, BM, BN, 2, 2>(d, stream, query);
     return launch_wgrad_impl<T, BM, BN, 2, 1>(d, stream, query);
 }
 
 template <typename T, int BM>
 int dispatch_wgrad_n(const DykWgradDesc* d, hipStream_t s, int* query) {
-    const bool cap64 = ((d->tune >> 24) & 0xf) == 1;        // bits 24..27 = 1: tiles capped at 64 x 64 (small GEMMs: more
-                                                            // tiles, so fewer K splits -- partial planes -- fill the chip)
+    const bool cap64 = wg_tune_cap64(d->tune);
     if (d->Cin > 64 && !cap64) return launch_wgrad<T, BM, 128>(d, s, query);
     if (d->Cin > 32) return launch_wgrad<T, BM, 64>(d, s, query);
     return launch_wgrad<T, BM, 32>(d, s, query);
 }
 template <typename T>
 int dispatch_wgrad(const DykWgradDesc* d, hipStream_t s, int* query) {
-    const bool cap64 = ((d->tune >> 24) & 0xf) == 1;
+    const bool cap64 = wg_tune_cap64(d->tune);
     if (d->Cout > 64 && !cap64) return dispatch_wgrad_n<T, 128>(d, s, query);
     if (d->Cout > 32) return dispatch_wgrad_n<T, 64>(d, s, query);
     return dispatch_wgrad_n<T, 32>(d, s, query);
@@ -476,12 +461,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_mt_kernel(const WgArgs args, c
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni) acc[t][mi][ni] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-    auto tr_read = [&](const char* p0, const char* p1) -> uint4 {
-        v4i16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)p0);
-        v4i16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)p1);
-        uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-        return make_uint4(l2.x, l2.y, h2.x, h2.y);
-    };
     auto compute = [&](const char* pa, const char* pb) {
         const int i16 = lane & 15, kq = lane >> 4;
 #pragma unroll
@@ -491,7 +470,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_mt_kernel(const WgArgs args, c
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
                 const int ch = wm * 32 + mi * 16 + 4 * (i16 & 3);
-                fa[mi] = tr_read(pa + wg_off<T, BM>(r0, ch), pa + wg_off<T, BM>(r0 + 4, ch));
+                fa[mi] = wg_tr_read(pa + wg_off<T, BM>(r0, ch), pa + wg_off<T, BM>(r0 + 4, ch));
             }
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
@@ -500,7 +479,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_mt_kernel(const WgArgs args, c
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) {
                     const int ch = wn * WTN + ni * 16 + 4 * (i16 & 3);
-                    fb[ni] = tr_read(pb + wg_off<T, BN>(h0, ch), pb + wg_off<T, BN>(h0 + 4 * SI, ch));
+                    fb[ni] = wg_tr_read(pb + wg_off<T, BN>(h0, ch), pb + wg_off<T, BN>(h0 + 4 * SI, ch));
                 }
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi)
@@ -599,14 +578,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_mt_kernel(const WgArgs args, c
 // the multi-tap kernel covers: bf16, the standard 3x3 / pad 1 tap table, stride 1 | 2, Wo a multiple of 32, whole 8-channel
 // vectors, plain [tap][Cout][Cin] gradient rows
 bool mt_eligible(const DykWgradDesc* d) {
-    if (d->dtype != DYK_BF16 || d->ntaps != 9 || d->isy != d->isx || (d->isy != 1 && d->isy != 2)) return false;
+    if (d->dtype != DYK_BF16 || !wg_std3x3_taps(d) || d->isy != d->isx || (d->isy != 1 && d->isy != 2)) return false;
     // (Wo need not be a multiple of the 32-pixel segment: ragged last segments are zero filled -- 80-, 40- and 20-pixel rows
     // of the deep stages waste 17 / 37 / 37 % of the MFMA work of a row but stage dy and x once for all nine taps)
     constexpr bool ragged = true;
-    if (d->Wo < 16 || (!ragged && d->Wo % 32) || d->Cin % 8 || d->Cout % 8 || (d->lddw > 0 && d->lddw != d->Cin)) return false;
-    for (int t = 0; t < 9; ++t)
-        if (d->tdy[t] != t / 3 - 1 || d->tdx[t] != t % 3 - 1) return false;
-    return true;
+    return !(d->Wo < 16 || (!ragged && d->Wo % 32) || d->Cin % 8 || d->Cout % 8 || (d->lddw > 0 && d->lddw != d->Cin));
 }
 
 template <int BN, int SI, int KW>
@@ -617,15 +593,9 @@ int launch_wgrad_mt(const DykWgradDesc* d, hipStream_t stream, int* query) {
     static_assert(lds <= 160 * 1024, "LDS budget");
     const int tiles = dyk_div_up(d->Cout, 64) * dyk_div_up(d->Cin, BN);
     const int nseg = d->B * d->Ho * ((d->Wo + KW - 1) / KW);
-    int splits = d->splits;
-    if (splits <= 0) {
-        splits = dyk_div_up(512, tiles);
-        const int max_splits = nseg / 16 > 0 ? nseg / 16 : 1;          // at least 16 segments per workgroup
-        if (splits > max_splits) splits = max_splits;
-    }
-    if (splits > nseg) splits = nseg;
-    const int chunk = dyk_div_up(nseg, splits);
-    if (!(d->part && d->splits > 0)) splits = dyk_div_up(nseg, chunk);
+    // 512 workgroups, at least 16 segments per workgroup
+    const WgSplitPlan p = wg_plan_splits(nseg, tiles, 512, 16, 1, d->splits, d->part && d->splits > 0);
+    const int splits = p.splits, chunk = p.chunk;
     if (query) { *query = splits; return DYK_OK; }
     static DykDeviceOnce attr_set;   // (the attribute is per DEVICE: one flag per device id; after the query path: no device there)
     auto kfn = conv_wgrad_mt_kernel<BN, SI, KW>;
@@ -689,17 +659,43 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(float* __restrict__ G,
 
 }  // namespace
 
-// row-block 3x3 kernel (conv_wgrad_rb.hip): tune bits 28..30 == 2; bits 8..15 == 2 selects 256-pixel K steps
+// row-block 3x3 kernel (conv_wgrad_rb.hip): variant 2; K-groups field == 2 selects 256-pixel K steps
 bool dyk_wgrad_rb_eligible(const DykWgradDesc* d);
 int dyk_wgrad_rb_dispatch(const DykWgradDesc* d, hipStream_t s, int* query);
-// pixel-streaming 1x1 kernel (conv_wgrad_ps.hip): tune bits 28..30 == 3
+// pixel-streaming 1x1 kernel (conv_wgrad_ps.hip): variant 3
 bool dyk_wgrad_ps_eligible(const DykWgradDesc* d);
 int dyk_wgrad_ps_dispatch(const DykWgradDesc* d, hipStream_t s, int* query_splits, int* query_tiles, int64_t* query_slab);
 
+// the kernel that runs `d`: the one its tune word asks for where the problem is eligible for it, else the per-tap kernel
+static int wgrad_variant(const DykWgradDesc* d) {
+    switch (wg_tune_variant(d->tune)) {
+    case 1: return mt_eligible(d) ? 1 : 0;
+    case 2: return dyk_wgrad_rb_eligible(d) ? 2 : 0;
+    case 3: return dyk_wgrad_ps_eligible(d) ? 3 : 0;
+    default: return 0;
+    }
+}
+
+// query != NULL: only report the split count the launch would use (no device is touched)
+static int wgrad_dispatch(const DykWgradDesc* d, hipStream_t s, int* query) {
+    switch (wgrad_variant(d)) {
+    case 1: return dispatch_wgrad_mt(d, s, query);
+    case 2: return dyk_wgrad_rb_dispatch(d, s, query);
+    case 3: return dyk_wgrad_ps_dispatch(d, s, query, nullptr, nullptr);
+    default: break;
+    }
+    if (d->dtype == DYK_BF16) return dispatch_wgrad<bf16_t>(d, s, query);
+    if (d->dtype == DYK_F32) return dispatch_wgrad<float>(d, s, query);
+    return DYK_ERR_ARG;
+}
+
+static bool wgrad_taps_ok(const DykWgradDesc* d) { return d && d->ntaps > 0 && d->ntaps <= DYK_MAX_TAPS; }
+static bool wgrad_shape_ok(const DykWgradDesc* d) {
+    return wgrad_taps_ok(d) && d->B > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0 && d->Cin > 0;
+}
+
 static int wgrad_validate(const DykWgradDesc* d) {
-    if (!d || !d->x || !d->dy || !d->dw) return DYK_ERR_ARG;
-    if (d->ntaps <= 0 || d->ntaps > DYK_MAX_TAPS) return DYK_ERR_ARG;
-    if (d->B <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0 || d->Cin <= 0) return DYK_ERR_ARG;
+    if (!wgrad_shape_ok(d) || !d->x || !d->dy || !d->dw) return DYK_ERR_ARG;
     const int epv = d->dtype == DYK_BF16 ? 8 : 4;
     // every 16-byte load must stay inside its pixel row: ld >= round_up(C, epv)
     if (d->ldx % epv || d->lddy % epv) return DYK_ERR_ARG;
@@ -719,54 +715,35 @@ extern "C" int dyk_conv_wgrad(const DykWgradDesc* d, void* stream) {
         const size_t lo = offsetof(DykWgradDesc, part_stride), hi = offsetof(DykWgradDesc, twin);
         if (memcmp((const char*)d + lo, (const char*)d->twin + lo, hi - lo) != 0 || (!d->part) != (!d->twin->part)) return DYK_ERR_ARG;
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (((d->tune >> 28) & 7) == 1 && mt_eligible(d)) return dispatch_wgrad_mt(d, s, nullptr);    // multi-tap 3x3 variant
-    if (((d->tune >> 28) & 7) == 2 && dyk_wgrad_rb_eligible(d)) return dyk_wgrad_rb_dispatch(d, s, nullptr);   // row-block 3x3 variant
-    if (((d->tune >> 28) & 7) == 3 && dyk_wgrad_ps_eligible(d)) return dyk_wgrad_ps_dispatch(d, s, nullptr, nullptr, nullptr);   // pixel-streaming 1x1 variant
-    if (d->sk_cnt && !d->part) return DYK_ERR_UNSUPPORTED;      // the in-launch fold exists in the pixel-streaming kernel only
-    if (d->group_n != 0) return DYK_ERR_UNSUPPORTED;            // grouped launches: pixel-streaming and row-block kernels only
-    if (d->dtype == DYK_BF16) return dispatch_wgrad<bf16_t>(d, s, nullptr);
-    if (d->dtype == DYK_F32) return dispatch_wgrad<float>(d, s, nullptr);
-    return DYK_ERR_ARG;
+    const int v = wgrad_variant(d);
+    if (v == 0 && d->sk_cnt && !d->part) return DYK_ERR_UNSUPPORTED;   // the in-launch fold exists in the pixel-streaming kernel only
+    if (v < 2 && d->group_n != 0) return DYK_ERR_UNSUPPORTED;          // grouped launches: pixel-streaming and row-block kernels only
+    return wgrad_dispatch(d, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int dyk_conv_wgrad_splits(const DykWgradDesc* d) {
-    if (!d || d->ntaps <= 0 || d->ntaps > DYK_MAX_TAPS || d->B <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0 || d->Cin <= 0)
-        return DYK_ERR_ARG;
+    if (!wgrad_shape_ok(d)) return DYK_ERR_ARG;
     int q = 0;
-    int rc = DYK_ERR_ARG;
-    if (((d->tune >> 28) & 7) == 1 && mt_eligible(d)) rc = dispatch_wgrad_mt(d, nullptr, &q);
-    else if (((d->tune >> 28) & 7) == 2 && dyk_wgrad_rb_eligible(d)) rc = dyk_wgrad_rb_dispatch(d, nullptr, &q);
-    else if (((d->tune >> 28) & 7) == 3 && dyk_wgrad_ps_eligible(d)) rc = dyk_wgrad_ps_dispatch(d, nullptr, &q, nullptr, nullptr);
-    else if (d->dtype == DYK_BF16) rc = dispatch_wgrad<bf16_t>(d, nullptr, &q);
-    else if (d->dtype == DYK_F32) rc = dispatch_wgrad<float>(d, nullptr, &q);
+    const int rc = wgrad_dispatch(d, nullptr, &q);
     return rc == DYK_OK ? q : rc;
 }
 
 extern "C" int dyk_conv_wgrad_variant(const DykWgradDesc* d) {
-    if (!d || d->ntaps <= 0 || d->ntaps > DYK_MAX_TAPS) return DYK_ERR_ARG;
-    if (((d->tune >> 28) & 7) == 1 && mt_eligible(d)) return 1;
-    if (((d->tune >> 28) & 7) == 2 && dyk_wgrad_rb_eligible(d)) return 2;
-    if (((d->tune >> 28) & 7) == 3 && dyk_wgrad_ps_eligible(d)) return 3;
-    return 0;
+    return wgrad_taps_ok(d) ? wgrad_variant(d) : DYK_ERR_ARG;
 }
 
 extern "C" int64_t dyk_conv_wgrad_fold_ws_bytes(const DykWgradDesc* d, int32_t* tiles) {
-    if (!d || d->ntaps <= 0 || d->ntaps > DYK_MAX_TAPS || d->B <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0 || d->Cin <= 0)
-        return DYK_ERR_ARG;
+    if (!wgrad_shape_ok(d)) return DYK_ERR_ARG;
     if (tiles) *tiles = 0;
     if (d->splits < 2) return 0;
+    if (wgrad_variant(d) != 3) return 0;          // kernels without the in-launch fold
     int sp = 0, nt = 0;
     int64_t slab = 0;
-    if (((d->tune >> 28) & 7) == 3 && dyk_wgrad_ps_eligible(d)) {
-        DykWgradDesc q = *d;                      // (the count as the fold mode will see it: `splits` taken literally)
-        q.part = nullptr;
-        uint32_t dummy = 0;
-        q.sk_cnt = &dummy;
-        if (dyk_wgrad_ps_dispatch(&q, nullptr, &sp, &nt, &slab) != DYK_OK) return DYK_ERR_ARG;
-    } else {
-        return 0;                                 // kernels without the in-launch fold
-    }
+    DykWgradDesc q = *d;                          // (the count as the fold mode will see it: `splits` taken literally)
+    q.part = nullptr;
+    uint32_t dummy = 0;
+    q.sk_cnt = &dummy;
+    if (dyk_wgrad_ps_dispatch(&q, nullptr, &sp, &nt, &slab) != DYK_OK) return DYK_ERR_ARG;
     if (sp < 2) return 0;
     if (tiles) *tiles = nt;
     return (int64_t)nt * sp * slab;

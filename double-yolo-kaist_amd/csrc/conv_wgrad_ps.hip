@@ -66,14 +66,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_ps_kernel(const DykWgradDesc a
     const int tiles_n = (Cin_s + BN - 1) / BN;
     // consecutive remapped ids run on one XCD: the tiles of one pixel range share that XCD's L2
     int bid = xcd_remap(blockIdx.x, gridDim.x);
-    // grouped launch: problem p owns blocks [p per, (p + 1) per); its tensors come out of the device table (scalar loads)
     const void *x_p = a.x, *dy_p = a.dy;
     float *dw_p = a.dw, *part_p = a.part;
     if (a.group_n > 0) {
-        const int per = tiles_m * tiles_n * splits;
-        const int prob = __builtin_amdgcn_readfirstlane(bid / per);
-        bid -= prob * per;
-        const DykWgradGroupEntry* e = wg_sgpr_ptr(a.group) + prob;
+        const DykWgradGroupEntry* e = wg_group_select(a.group, tiles_m, tiles_n, splits, bid);
         x_p = e->x; dy_p = e->dy; dw_p = e->dw; part_p = e->part;
     }
     const int tile = bid % (tiles_m * tiles_n);
@@ -94,12 +90,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_ps_kernel(const DykWgradDesc a
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-    auto tr_read = [&](const char* p0, const char* p1) -> uint4 {
-        v4i16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)p0);
-        v4i16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)p1);
-        uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-        return make_uint4(l2.x, l2.y, h2.x, h2.y);
-    };
     auto compute = [&](const char* pa) {
         const char* pb = pa + C::A_BYTES;
         const int i16 = lane & 15, kq = lane >> 4;
@@ -110,12 +100,12 @@ __global__ __launch_bounds__(512) void conv_wgrad_ps_kernel(const DykWgradDesc a
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
                 const int ch = wm * WTM + mi * 16 + 4 * (i16 & 3);
-                fa[mi] = tr_read(pa + wg_off<T, BM>(r0, ch), pa + wg_off<T, BM>(r0 + 4, ch));
+                fa[mi] = wg_tr_read(pa + wg_off<T, BM>(r0, ch), pa + wg_off<T, BM>(r0 + 4, ch));
             }
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni) {
                 const int ch = wn * WTN + ni * 16 + 4 * (i16 & 3);
-                fb[ni] = tr_read(pb + wg_off<T, BN>(r0, ch), pb + wg_off<T, BN>(r0 + 4, ch));
+                fb[ni] = wg_tr_read(pb + wg_off<T, BN>(r0, ch), pb + wg_off<T, BN>(r0 + 4, ch));
             }
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
@@ -236,7 +226,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_ps_kernel(const DykWgradDesc a
     // ---- results: fin[ml][ni][r] = D[co = m0 + wm WTM + (g MH + ml) 16 + (lane >> 4) 4 + r][ci = n0 + wn WTN + ni 16 + (lane & 15)]
     const int lddw = a.lddw > 0 ? a.lddw : Cin_s;
     const long toff = (long)a.twt[0] * Cout_s * lddw;
-    const bool exclusive = (a.tune >> 20) & 1;
+    const bool exclusive = wg_tune_exclusive(a.tune);
     bool rmw = exclusive && splits == 1;          // single writer, single split: read-add-write instead of atomics
     float* dst = dw_p + toff;
     bool plain = false;
@@ -316,21 +306,13 @@ PsPlan ps_plan(const DykWgradDesc* d) {
     const long Ntot = (long)d->B * d->Ho * d->Wo;
     p.kr = KR;
     p.tiles = dyk_div_up(d->Cout, BM) * dyk_div_up(d->Cin, BN);
-    const int ksteps = dyk_div_up(Ntot, KR);
-    int splits = d->splits;
-    if (splits <= 0) {
-        // one 8-wave workgroup per CU, every workgroup at least four stages
-        splits = dyk_div_up(256, p.tiles);
-        const int max_splits = ksteps / 4 > 0 ? ksteps / 4 : 1;
-        if (splits > max_splits) splits = max_splits;
-    }
-    if (splits > ksteps) splits = ksteps;
-    p.chunk = dyk_div_up(ksteps, splits) * KR;
+    // one 8-wave workgroup per CU, every workgroup at least four stages; the fold mode takes a given count literally too
+    const bool literal = (d->part || d->sk_cnt) && d->splits > 0;
+    const WgSplitPlan sp = wg_plan_splits(dyk_div_up(Ntot, KR), p.tiles, 256, 4, 1, d->splits, literal);
+    p.chunk = sp.chunk * KR;
     // (plane / fold mode with a given count: exactly that many slices are written, trailing empty ones with zeros -- also when
-    // the count exceeds the number of stages)
-    if ((d->part || d->sk_cnt) && d->splits > 0) splits = d->splits;
-    else splits = dyk_div_up(Ntot, p.chunk);
-    p.splits = splits;
+    // the count exceeds the number of stages, unlike the other three kernels, which clamp it to the steps)
+    p.splits = literal ? d->splits : sp.splits;
     return p;
 }
 
@@ -354,12 +336,11 @@ int launch_ps(const DykWgradDesc* d, hipStream_t stream, PsPlan* query) {
     return DYK_OK;
 }
 
-// tune word (bits 28..30 == 3 selects this kernel): bits 0..7 ring stages (0 = default), bits 8..11 tile cap (1 = 64 x 64),
-// bits 12..15 pixels per stage (0 = by tile, 1 = 64, 2 = 128)
+// tune word (variant 3 selects this kernel): ring stages (0 = default), ps_tune_cap64, ps_tune_stage_len
 template <int BM, int BN, int KR>
 int dispatch_ps_ns(const DykWgradDesc* d, hipStream_t s, PsPlan* q) {
     constexpr int STAGE = KR * (BM + BN) * 2;
-    int ns = d->tune & 0xff;
+    int ns = wg_tune_stages(d->tune);
     if (ns <= 0) ns = 4;
     if constexpr (STAGE == 16 * 1024) {
         if (ns >= 8) return launch_ps<BM, BN, KR, 8>(d, s, q);
@@ -378,8 +359,8 @@ int dispatch_ps_ns(const DykWgradDesc* d, hipStream_t s, PsPlan* q) {
 }
 
 int dispatch_ps(const DykWgradDesc* d, hipStream_t s, PsPlan* q) {
-    const bool cap64 = ((d->tune >> 8) & 0xf) == 1;
-    const int krc = (d->tune >> 12) & 0xf;
+    const bool cap64 = ps_tune_cap64(d->tune);
+    const int krc = ps_tune_stage_len(d->tune);
     const bool m128 = d->Cout > 64 && !cap64, n128 = d->Cin > 64 && !cap64;
     if (m128 && n128) return dispatch_ps_ns<128, 128, 64>(d, s, q);
     if (m128) return dispatch_ps_ns<128, 64, 64>(d, s, q);
@@ -405,7 +386,7 @@ int dyk_wgrad_ps_dispatch(const DykWgradDesc* d, hipStream_t s, int* query_split
         if (query_splits) *query_splits = p.splits;
         if (query_tiles) *query_tiles = p.tiles;
         if (query_slab) {
-            const bool cap64 = ((d->tune >> 8) & 0xf) == 1;
+            const bool cap64 = ps_tune_cap64(d->tune);
             const int bm = d->Cout > 64 && !cap64 ? 128 : 64, bn = d->Cin > 64 && !cap64 ? 128 : 64;
             *query_slab = (int64_t)bm * bn * 4;
         }

@@ -26,14 +26,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
-#include "dyk_common.h"
+#include "conv_wgrad_tile.h"
 
 namespace {
-
-typedef short v4i16_t __attribute__((__vector_size__(4 * sizeof(short))));
-#define LDS_AS __attribute__((address_space(3)))
-
-__device__ uint4 dyk_rb_zero_page[8];
 
 struct RbGeom {
     int nimg, rh, wseg;      // output pixels of a K step: nimg x rh x wseg  (= KP)
@@ -41,22 +36,6 @@ struct RbGeom {
     int nbx, nby, nsteps;    // blocks per row / per column of blocks, K steps of the whole problem
     int si;
 };
-
-__device__ inline void rb_glds16(const void* gsrc, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_addr)
-                 : "memory");
-}
-__device__ inline unsigned rb_lds_addr(const void* p) {
-    return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(LDS_AS const char*)p);
-}
-template <typename P> __device__ inline P* rb_sgpr_ptr(P* p) {
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (P*)(((unsigned long long)hi << 32) | lo);
-}
 
 // byte offset of (row, 32-byte chunk) in the dy tile [KP][64 co] (128-byte rows) and in the x tile [rows][32 ci] (64-byte rows)
 __device__ inline int rb_a_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 3)) << 5); }
@@ -98,14 +77,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_rb_kernel(const DykWgradDesc a
     const int tiles_n = (a.Cin + RB_BN - 1) / RB_BN;
     // consecutive remapped ids share an XCD: the channel tiles of one pixel range read the same dy / x lines through one L2
     int bid = xcd_remap(blockIdx.x, gridDim.x);
-    // grouped launch (DykWgradDesc.group): problem p owns blocks [p per, (p + 1) per); its tensors come out of the device table
     const void *x_p = a.x, *dy_p = a.dy;
     float *dw_p = a.dw, *part_p = a.part;
     if (a.group_n > 0) {
-        const int per = tiles_m * tiles_n * splits;
-        const int prob = __builtin_amdgcn_readfirstlane(bid / per);
-        bid -= prob * per;
-        const DykWgradGroupEntry* e = rb_sgpr_ptr(a.group) + prob;
+        const DykWgradGroupEntry* e = wg_group_select(a.group, tiles_m, tiles_n, splits, bid);
         x_p = e->x; dy_p = e->dy; dw_p = e->dw; part_p = e->part;
     }
     const int tm = bid % tiles_m; bid /= tiles_m;
@@ -115,8 +90,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_rb_kernel(const DykWgradDesc a
     const int g_begin = sp * chunk;
     const int g_end = min(g.nsteps, g_begin + chunk);
     const int S = g_end > g_begin ? g_end - g_begin : 0;
-    const T* __restrict__ dyg = rb_sgpr_ptr((const T*)dy_p);
-    const T* __restrict__ xg = rb_sgpr_ptr((const T*)x_p);
+    const T* __restrict__ dyg = wg_sgpr_ptr((const T*)dy_p);
+    const T* __restrict__ xg = wg_sgpr_ptr((const T*)x_p);
 
     const int Cout_s = __builtin_amdgcn_readfirstlane(a.Cout), Cin_s = __builtin_amdgcn_readfirstlane(a.Cin);
     const int lddy_s = __builtin_amdgcn_readfirstlane(a.lddy), ldx_s = __builtin_amdgcn_readfirstlane(a.ldx);
@@ -154,7 +129,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_rb_kernel(const DykWgradDesc a
     //      slot i of that kilobyte, the swizzle is applied on the source side (logical channel of the physical slot).
     //      Per slot ONE element offset relative to the step's origin pixel (dy: negative = channel beyond Cout -> zero page)
     //      and, for x, the halo coordinates packed into one register for the border test.
-    const T* zero = (const T*)dyk_rb_zero_page;
+    const T* zero = (const T*)dyk_wg_zero_page;
     int a_eoff[NAW];
 #pragma unroll
     for (int j = 0; j < NAW; ++j) {
@@ -192,7 +167,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_rb_kernel(const DykWgradDesc a
         for (int j = 0; j < NAW; ++j) {
             const T* cand = dy0 + a_eoff[j];
             const T* src = a_eoff[j] >= 0 ? cand : zero;
-            rb_glds16(src, rb_lds_addr(da + (j * 8 + wv) * 1024));
+            wg_glds16(src, wg_lds_addr(da + (j * 8 + wv) * 1024));
         }
 #pragma unroll
         for (int j = 0; j < NXW; ++j) {
@@ -200,7 +175,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_rb_kernel(const DykWgradDesc a
             const bool ok = ((unsigned)(ys + hy) < (unsigned)Hi_s) & ((unsigned)(xs + hx) < (unsigned)Wi_s);
             const T* cand = x00 + b_eoff[j];
             const T* src = ok ? cand : zero;
-            rb_glds16(src, rb_lds_addr(db + (j * 8 + wv) * 1024));
+            wg_glds16(src, wg_lds_addr(db + (j * 8 + wv) * 1024));
         }
         if (++bx == g.nbx) { bx = 0; if (++by == g.nby) { by = 0; ++bb; } }
     };
@@ -211,21 +186,16 @@ __global__ __launch_bounds__(512) void conv_wgrad_rb_kernel(const DykWgradDesc a
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) acc[t][mi] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-    auto tr_read = [&](const char* p0, const char* p1) -> bf16x8_t {
-        v4i16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)p0);
-        v4i16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS v4i16_t*)(LDS_AS char*)p1);
-        uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-        return __builtin_bit_cast(bf16x8_t, make_uint4(l2.x, l2.y, h2.x, h2.y));
-    };
     auto compute = [&](const char* ps) {
 #pragma unroll
         for (int w = 0; w < KKW; ++w) {
             bf16x8_t fa[4];
 #pragma unroll
-            for (int mi = 0; mi < 4; ++mi) fa[mi] = tr_read(ps + (aoff[w][0] ^ (mi << 5)), ps + (aoff[w][1] ^ (mi << 5)));
+            for (int mi = 0; mi < 4; ++mi)
+                fa[mi] = __builtin_bit_cast(bf16x8_t, wg_tr_read(ps + (aoff[w][0] ^ (mi << 5)), ps + (aoff[w][1] ^ (mi << 5))));
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
-                const bf16x8_t fb = tr_read(ps + boff[w][0][t], ps + boff[w][1][t]);
+                const bf16x8_t fb = __builtin_bit_cast(bf16x8_t, wg_tr_read(ps + boff[w][0][t], ps + boff[w][1][t]));
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi)
                     acc[t][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mi], fb, acc[t][mi], 0, 0, 0);
@@ -243,7 +213,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_rb_kernel(const DykWgradDesc a
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    const bool abl_noloop = (a.tune >> 17) & 1;                // analysis switch (tools/gpu_probe.py), never set by the plan
+    const bool abl_noloop = wg_tune_abl_noloop(a.tune);
     const int SL = abl_noloop ? 0 : S;
 #pragma unroll
     for (int i = 0; i < AHEAD; ++i)
@@ -300,9 +270,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_rb_kernel(const DykWgradDesc a
     const int lddw = a.Cin;
     const bool plane = part_p != nullptr;
     float* out = plane ? part_p + (long)sp * a.part_stride : dw_p;
-    // one K split and a caller that vouches for it (tune bit 20: nobody else adds to dw while this launch runs): every
+    // one K split and a caller that vouches for it (wg_tune_exclusive: nobody else adds to dw while this launch runs): every
     // gradient element has exactly one writer, read-add-write replaces 4.7 M atomics on the 16x20 layers (53 -> 8 us)
-    const bool rmw = !plane && splits == 1 && ((a.tune >> 20) & 1);
+    const bool rmw = !plane && splits == 1 && wg_tune_exclusive(a.tune);
     const bool vec = (plane || rmw) && ((((size_t)out) | ((size_t)lddw * 4) | ((size_t)a.Cout * lddw * 4)) & 15) == 0;
     if (vec) {
         const int row = tid >> 3, c4 = (tid & 7) * 4;
@@ -373,16 +343,10 @@ template <int KKW, int NXW>
 int rb_launch(const DykWgradDesc* d, const RbGeom& g, hipStream_t stream, int* query) {
     using C = RbCfg<KKW, NXW>;
     const int tiles = dyk_div_up(d->Cout, RB_BM) * dyk_div_up(d->Cin, RB_BN);
-    int splits = d->splits;
-    if (splits <= 0) {
-        constexpr int target = 256;                            // (128 ... 384 workgroups: +-0.1 ms in the step, round 4)
-        splits = dyk_div_up(target, tiles);                    // one workgroup (8 waves, its LDS) per CU
-        const int max_splits = g.nsteps / 4 > 0 ? g.nsteps / 4 : 1;
-        if (splits > max_splits) splits = max_splits;
-    }
-    if (splits > g.nsteps) splits = g.nsteps;
-    const int chunk = dyk_div_up(g.nsteps, splits);
-    if (!(d->part && d->splits > 0)) splits = dyk_div_up(g.nsteps, chunk);
+    constexpr int target = 256;                                // one workgroup (8 waves, its LDS) per CU
+                                                               // (128 ... 384 workgroups: +-0.1 ms in the step, round 4)
+    const WgSplitPlan p = wg_plan_splits(g.nsteps, tiles, target, 4, 1, d->splits, d->part && d->splits > 0);
+    const int splits = p.splits, chunk = p.chunk;
     if (query) { *query = splits; return DYK_OK; }
     if (d->group_n < 0 || d->group_n == 1 || (d->group_n > 0 && !d->group)) return DYK_ERR_ARG;
     static DykDeviceOnce attr_set;   // (the attribute is per DEVICE: one flag per device id; after the query path: no device there)
@@ -415,11 +379,9 @@ int rb_dispatch_n(const DykWgradDesc* d, const RbGeom& g, hipStream_t s, int* qu
 
 // 0 = the row-block kernel does not cover this problem (the caller falls back to the per-tap kernel)
 bool dyk_wgrad_rb_eligible(const DykWgradDesc* d) {
-    if (d->dtype != DYK_BF16 || d->ntaps != 9 || d->isy != d->isx || (d->isy != 1 && d->isy != 2) || d->twin) return false;
+    if (d->dtype != DYK_BF16 || !wg_std3x3_taps(d) || d->isy != d->isx || (d->isy != 1 && d->isy != 2) || d->twin) return false;
     if (d->Cin % 8 || d->Cout % 8 || (d->lddw > 0 && d->lddw != d->Cin)) return false;
-    for (int t = 0; t < 9; ++t)
-        if (d->tdy[t] != t / 3 - 1 || d->tdx[t] != t % 3 - 1) return false;
-    const int kkw = ((d->tune >> 8) & 0xff) == 2 ? 2 : 1;
+    const int kkw = wg_tune_kgroups(d->tune) == 2 ? 2 : 1;
     RbGeom g;
     if (!rb_geometry(d, 128 * kkw, &g)) return false;
     const int nxw = dyk_div_up(g.hp, 128);
@@ -427,7 +389,7 @@ bool dyk_wgrad_rb_eligible(const DykWgradDesc* d) {
 }
 
 int dyk_wgrad_rb_dispatch(const DykWgradDesc* d, hipStream_t s, int* query) {
-    const int kkw = ((d->tune >> 8) & 0xff) == 2 ? 2 : 1;
+    const int kkw = wg_tune_kgroups(d->tune) == 2 ? 2 : 1;
     RbGeom g;
     if (!rb_geometry(d, 128 * kkw, &g)) return DYK_ERR_UNSUPPORTED;
     return kkw == 2 ? rb_dispatch_n<2>(d, g, s, query) : rb_dispatch_n<1>(d, g, s, query);

@@ -1666,7 +1666,7 @@ def _default_wgrad_tunes(plan):
     for op, d in plan.bwd:
         if op != L.OP_WGRAD or d.tune:
             continue
-        for v, t in ((2, 2 | (1 << 8) | (2 << 28) | WGRAD_EXCLUSIVE), (3, (3 << 28) | 3 | WGRAD_EXCLUSIVE)):
+        for v, t in ((2, WGRAD_RB | 2 | WGRAD_KG1 | WGRAD_EXCLUSIVE), (3, WGRAD_PS | 3 | WGRAD_EXCLUSIVE)):
             d.tune = t
             if (v == 2 and os.environ.get("DYK_WGRAD_RB", "1") == "0") or (v == 3 and os.environ.get("DYK_WGRAD_PS", "1") == "0") \
                     or lib.dyk_conv_wgrad_variant(ctypes.byref(d)) != v:
@@ -1743,7 +1743,8 @@ def _group_wgrads(plan, store):
     first_off = {}
     for e in store.entries:
         first_off.setdefault(e.layer, e.offset)
-    cuts = [total - int(f * total) for f in (0.5, 0.8, 0.95, 0.99)]
+    from .ddp import GradAllReduce
+    cuts = [total - int(f * total) for f in GradAllReduce.GEOMETRIC]
     protected = []
     for k in range(1, len(marks)):
         c_end, layer_done = marks[k][0], marks[k - 1][1]
@@ -1771,7 +1772,7 @@ def _group_wgrads(plan, store):
     def tiles_of(d):                          # workgroups of one problem per K split
         if lib.dyk_conv_wgrad_variant(ctypes.byref(d)) == 2:
             return -(-d.Cout // 64) * -(-d.Cin // 32)
-        cap64 = ((d.tune >> 8) & 0xf) == 1
+        cap64 = bool(d.tune & WGRAD_PS_CAP64)
         bm, bn = (128 if d.Cout > 64 and not cap64 else 64), (128 if d.Cin > 64 and not cap64 else 64)
         return -(-d.Cout // bm) * -(-d.Cin // bn)
 
@@ -2122,23 +2123,36 @@ def _conv_split_candidates(d):
     return out
 
 
+# DykWgradDesc.tune (decoded in csrc/conv_wgrad_tile.h; the layout is persisted in bench_tuning.json and in tune caches):
+# LDS ring stages in the low byte (2 | 3; 4 exists in the kernel, measured never the fastest: DESIGN 9.4) | K-groups per
+# workgroup << 8 | tile cap << 24 (1 = 64 x 64) | the kernel variant << 28, ignored where it does not apply
+WGRAD_KG1, WGRAD_KG2 = 1 << 8, 2 << 8
+WGRAD_CAP64 = 1 << 24
+WGRAD_MT = 1 << 28             # multi-tap 3x3 kernel
+WGRAD_RB = 2 << 28             # row-block 3x3 kernel (round 4: 128-pixel block steps, 64 x 32 x 9-tap tiles)
+# pixel-streaming 1x1 kernel (round 6, csrc/conv_wgrad_ps.hip): ring stages in the low byte, 64 x 64 tile cap << 8,
+# 64-pixel stages for the 64 x 64 tile << 12; ignored (falls back to the per-tap kernel = candidate 2) where it does not apply
+WGRAD_PS = 3 << 28
+WGRAD_PS_CAP64, WGRAD_PS_STAGE64 = 1 << 8, 1 << 12
 WGRAD_EXCLUSIVE = 1 << 20      # the plan's weight gradients have one writer each (store.g_ptr per weight, commands ordered by
                                 # their write sets): a single-split row-block launch may read-add-write instead of atomics
-_WGRAD_CANDIDATES = [2, 3, 2 | (2 << 8), 2 | (1 << 24), 3 | (1 << 24), 2 | (2 << 8) | (1 << 24), 2 | (1 << 28)]
+
+
+def wgrad_variant(tune):
+    """the kernel a tune word asks for: 0 per-tap, 1 multi-tap (WGRAD_MT), 2 row-block (WGRAD_RB), 3 pixel-streaming (WGRAD_PS)"""
+    return (tune >> 28) & 7
+
+
+_WGRAD_CANDIDATES = [2, 3, 2 | WGRAD_KG2, 2 | WGRAD_CAP64, 3 | WGRAD_CAP64, 2 | WGRAD_KG2 | WGRAD_CAP64, 2 | WGRAD_MT]
 if os.environ.get("DYK_WGRAD_RB", "1") != "0":
-    _WGRAD_CANDIDATES.append(2 | (1 << 8) | (2 << 28) | WGRAD_EXCLUSIVE)
+    _WGRAD_CANDIDATES.append(2 | WGRAD_KG1 | WGRAD_RB | WGRAD_EXCLUSIVE)
 if os.environ.get("DYK_WGRAD_PS", "1") != "0":
-    # pixel-streaming 1x1 kernel (round 6, csrc/conv_wgrad_ps.hip): ring stages in the low byte, 64 x 64 tile cap << 8,
-    # 64-pixel stages for the 64 x 64 tile << 12; ignored (falls back to the per-tap kernel = candidate 2) where it does not apply
-    _WGRAD_PS = 3 << 28
     # Rings of at most 96 KB: a weight gradient is filler work beside the critical chain, and a workgroup that holds 128 KB of
     # LDS keeps every convolution workgroup (45-110 KB) off its CU for its whole life.  Alone, the 4- / 6-stage rings are the
     # faster ones on the deep layers (tools/wgps_probe.py); in the step every launch forced to 2 / 3 / 4 stages measured
     # 26.35 / 26.42 / 26.46 ms against 26.53 with the tuner's free choice (r6_ab_ps_ring_in_step.log)
-    _WGRAD_CANDIDATES += [_WGRAD_PS | 2 | WGRAD_EXCLUSIVE, _WGRAD_PS | 3 | WGRAD_EXCLUSIVE,
-                          _WGRAD_PS | 4 | (1 << 8) | WGRAD_EXCLUSIVE, _WGRAD_PS | 4 | (1 << 8) | (1 << 12) | WGRAD_EXCLUSIVE]
-# LDS ring stages (2 | 3; 4 exists in the kernel, measured never the fastest: DESIGN 9.4) | K-groups per workgroup << 8 | tile cap << 24 (1 = 64 x 64) | 1 << 28 = multi-tap 3x3 kernel
-# | 2 << 28 = row-block 3x3 kernel (round 4: 128-pixel block steps, 64 x 32 x 9-tap tiles)
+    _WGRAD_CANDIDATES += [WGRAD_PS | 2 | WGRAD_EXCLUSIVE, WGRAD_PS | 3 | WGRAD_EXCLUSIVE,
+                          WGRAD_PS | 4 | WGRAD_PS_CAP64 | WGRAD_EXCLUSIVE, WGRAD_PS | 4 | WGRAD_PS_CAP64 | WGRAD_PS_STAGE64 | WGRAD_EXCLUSIVE]
 
 
 def _time_launch(fn, desc, stream, reps=3):
@@ -2274,7 +2288,7 @@ def autotune(plan, cache=None):
                     combos, times = [], []
                     for c in cands:
                         d.tune, d.part, d.part_stride, d.splits = c, None, 0, 0
-                        if (c >> 28) & 7 and lib.dyk_conv_wgrad_variant(ctypes.byref(d)) != (c >> 28) & 7:
+                        if wgrad_variant(c) and lib.dyk_conv_wgrad_variant(ctypes.byref(d)) != wgrad_variant(c):
                             continue           # a kernel variant this problem is not eligible for (it would time the fallback again)
                         auto = lib.dyk_conv_wgrad_splits(ctypes.byref(d))
                         if auto < 1:
@@ -2305,7 +2319,7 @@ def autotune(plan, cache=None):
 
                     def trial_w(c, reps=3):
                         d.tune = c
-                        if (c >> 28) & 7 and lib.dyk_conv_wgrad_variant(ctypes.byref(d)) != (c >> 28) & 7:
+                        if wgrad_variant(c) and lib.dyk_conv_wgrad_variant(ctypes.byref(d)) != wgrad_variant(c):
                             return float("inf")
                         return _time_launch(fn, d, stream, reps)
                     try:

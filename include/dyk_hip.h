@@ -260,7 +260,8 @@ typedef struct DykWgradDesc {
     /* Grouped launch (round 6; kernels: pixel-streaming 1x1, row-block 3x3): group_n >= 2 problems of THIS geometry / tune /
      * splits / part_stride in one launch -- the weight gradients of the repeated residual units of a stage, which become
      * ready one after the other and are nobody's input before the optimizer.  `group` is a DEVICE array of group_n entries
-     * (x, dy, dw, part per problem; this descriptor's own x / dy / dw / part are ignored); the workgroups of problem p are
+     * (x, dy, dw, part per problem; this descriptor's own x / dy / dw / part are validated like a single launch's and must equal
+     * one member's, part's NULL-ness included: it selects plane mode for the whole group); the workgroups of problem p are
      * blocks [p * tiles * splits, (p + 1) * tiles * splits).  Every problem's result is what its own launch would give, bit for
      * bit.  Not combinable with twin or the in-launch fold. */
     const DykWgradGroupEntry* group;

@@ -919,6 +919,17 @@ def test_grouped_weight_gradient_launch(k, case):
     bad.dw = grads[0].data_ptr()
     bad.group, bad.group_n = tab.data_ptr(), G
     assert lib.dyk_conv_wgrad(ctypes.byref(bad), None) != 0
+    if k == 3:
+        # nor does the multi-tap kernel (every 3x3 case here is eligible for it): refused before anything is launched, every
+        # member's gradient -- the lead's included -- keeps its bits
+        lead = members[-1]
+        lead.tune, lead.part, lead.part_stride, lead.splits = 2 | (1 << 28), None, 0, 1
+        assert lib.dyk_conv_wgrad_variant(ctypes.byref(lead)) == 1
+        before = [t.clone() for t in grads]
+        assert lib.dyk_conv_wgrad(ctypes.byref(lead), None) != 0
+        torch.cuda.synchronize()
+        for i in range(G):
+            assert torch.equal(grads[i], before[i]), i
 
 
 @pytest.mark.gpu
