@@ -4,10 +4,11 @@
 // small record), and step kernels that take skip / clip coefficient / bias corrections from that record instead of from the
 // host.  No atomics and no in-launch hand-off: the kernel boundary orders the partials before the fold, and the fold before
 // the step.  HBM-bound: 16-byte vectors, four loads in flight per lane; per loaded float one fp32 product, one conversion and
-// one fp64 FMA (a few per cent of the fp64 vector rate at HBM speed).  optim.hip is not touched: the update statements below
-// are copies of adam_kernel / sgd_kernel, in their order, so that an unclipped, unskipped step gives the same bits.
+// one fp64 FMA (a few per cent of the fp64 vector rate at HBM speed).  The update statements are the device functions of
+// optim_update.h that adam_kernel / sgd_kernel of optim.hip inline too, so that an unclipped, unskipped step gives the same bits.
 #include <float.h>
 #include "dyk_common.h"
+#include "optim_update.h"
 
 namespace {
 
@@ -159,7 +160,7 @@ __device__ __forceinline__ void clear_grads(const DykOptimDesc& d) {
         ((float4*)d.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// adam_kernel of optim.hip, statement for statement, with skip / grad_scale / bias corrections from the record
+// adam_kernel of optim.hip with skip / grad_scale / bias corrections from the record: the same device function per vector
 __global__ __launch_bounds__(256) void adam_guarded_kernel(DykOptimDesc d, const DykGradGuardRec* __restrict__ rec) {
     if (rec->skip) {
         clear_grads(d);
@@ -171,37 +172,14 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(DykOptimDesc d, const
     const float step_size = lr / bc1;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         if (d.mask && ((const uint32_t*)d.mask)[i] == 0) {      // frozen parameters (entries are 64-element aligned)
-            if (d.zero_grad) ((float4*)d.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            dyk_optim::clear_grad_vec(d, i);
             continue;
         }
-        float4 p = ((float4*)d.p)[i];
-        float4 g = ((const float4*)d.g)[i];
-        float4 m = ((float4*)d.m)[i];
-        float4 v = ((float4*)d.v)[i];
-        float* pp = (float*)&p; float* gg = (float*)&g; float* mm = (float*)&m; float* vv = (float*)&v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gr = gg[j] * gs;
-            if (wd != 0.f) gr += wd * pp[j];
-            mm[j] = b1 * mm[j] + (1.f - b1) * gr;                 // exp_avg.lerp_(grad, 1 - beta1)
-            vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;            // exp_avg_sq
-            const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-            pp[j] -= step_size * (mm[j] / denom);
-        }
-        ((float4*)d.p)[i] = p;
-        ((float4*)d.m)[i] = m;
-        ((float4*)d.v)[i] = v;
-        if (d.zero_grad) ((float4*)d.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (d.wc) {
-            uint2 pk;
-            pk.x = (uint32_t)f32_to_bf16(pp[0]) | ((uint32_t)f32_to_bf16(pp[1]) << 16);
-            pk.y = (uint32_t)f32_to_bf16(pp[2]) | ((uint32_t)f32_to_bf16(pp[3]) << 16);
-            ((uint2*)d.wc)[i] = pk;
-        }
+        dyk_optim::adam_vec(d, i, gs, wd, b1, b2, eps, bc2_sqrt, step_size, false, 1.f);
     }
 }
 
-// sgd_kernel of optim.hip, statement for statement; the first-step rule fires at the first APPLIED step
+// sgd_kernel of optim.hip; the first-step rule fires at the first APPLIED step
 __global__ __launch_bounds__(256) void sgd_guarded_kernel(DykOptimDesc d, const DykGradGuardRec* __restrict__ rec) {
     if (rec->skip) {
         clear_grads(d);
@@ -212,30 +190,10 @@ __global__ __launch_bounds__(256) void sgd_guarded_kernel(DykOptimDesc d, const 
     const float lr = d.lr, mom = d.beta1, wd = d.weight_decay, gs = __fmul_rn(d.grad_scale, rec->coef);
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         if (d.mask && ((const uint32_t*)d.mask)[i] == 0) {
-            if (d.zero_grad) ((float4*)d.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            dyk_optim::clear_grad_vec(d, i);
             continue;
         }
-        float4 p = ((float4*)d.p)[i];
-        float4 g = ((const float4*)d.g)[i];
-        float4 m = ((float4*)d.m)[i];
-        float* pp = (float*)&p; float* gg = (float*)&g; float* mm = (float*)&m;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gr = gg[j] * gs;
-            if (wd != 0.f) gr += wd * pp[j];
-            mm[j] = first_step ? gr : mom * mm[j] + gr;           // momentum buffer (dampening 0)
-            gr = gr + mom * mm[j];                                // nesterov
-            pp[j] -= lr * gr;
-        }
-        ((float4*)d.p)[i] = p;
-        ((float4*)d.m)[i] = m;
-        if (d.zero_grad) ((float4*)d.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (d.wc) {
-            uint2 pk;
-            pk.x = (uint32_t)f32_to_bf16(pp[0]) | ((uint32_t)f32_to_bf16(pp[1]) << 16);
-            pk.y = (uint32_t)f32_to_bf16(pp[2]) | ((uint32_t)f32_to_bf16(pp[3]) << 16);
-            ((uint2*)d.wc)[i] = pk;
-        }
+        dyk_optim::sgd_vec(d, i, gs, wd, mom, lr, first_step);
     }
 }
 

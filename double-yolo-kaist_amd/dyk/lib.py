@@ -183,6 +183,18 @@ class DykGradGuardRec(ctypes.Structure):
                 ("applied", _i32), ("skipped", _i32), ("bc1", _f32), ("bc2_sqrt", _f32)]
 
 
+OPT_MAX_GROUPS = 8                 # DYK_OPT_MAX_GROUPS
+OPT_GROUP_DECOUPLED = 1            # DYK_OPT_GROUP_DECOUPLED
+
+
+class DykOptimGroup(ctypes.Structure):
+    _fields_ = [("lr", _f32), ("weight_decay", _f32), ("decay_mul", _f32), ("flags", ctypes.c_uint32)]
+
+
+class DykOptimGroups(ctypes.Structure):
+    _fields_ = [("count", _i32), ("_pad", _i32 * 3), ("g", DykOptimGroup * OPT_MAX_GROUPS)]
+
+
 class DykGradStatsDesc(ctypes.Structure):
     _fields_ = [("g", _vp), ("mask", _vp), ("ws", _vp), ("rec", _vp), ("n", _i64), ("ws_bytes", _i64), ("grad_scale", _f32),
                 ("max_norm", _f32), ("beta1", _f32), ("beta2", _f32), ("skip_nonfinite", _i32), ("_pad", _i32)]
@@ -274,6 +286,8 @@ SIGNATURES = {
     "dyk_adam_step_guarded": (_i32, [_P(DykOptimDesc), _vp, _vp]),
     "dyk_sgd_step_guarded": (_i32, [_P(DykOptimDesc), _vp, _vp]),
     "dyk_grad_scale_by_rec": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "dyk_adam_step_groups": (_i32, [_P(DykOptimDesc), _P(DykOptimGroups), _vp, _vp]),
+    "dyk_sgd_step_groups": (_i32, [_P(DykOptimDesc), _P(DykOptimGroups), _vp, _vp]),
     "dyk_ema_update": (_i32, [_P(DykEmaDesc), _vp]),
     "dyk_run_commands_timed": (_i32, [_P(DykCommand), _i32, _vp, _P(_f32)]),
     "dyk_loss_scale_grads": (_i32, [_vp, _i64, _i32, _vp, _vp]),

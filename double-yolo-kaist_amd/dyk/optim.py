@@ -9,19 +9,130 @@ rule, same constructor arguments, `step()` / `zero_grad()` / `param_groups[0]['l
 Opt-in protection (`max_grad_norm=`, `skip_nonfinite=`): what the reference harness gets from amp.GradScaler
 (train_utils/kaist_train_eval_utils.py:44,103-108) and torch.nn.utils.clip_grad_norm_, decided on the device from one
 reduction over the flat gradient buffer (csrc/optim_guard.hip) -- no per-tensor kernels, no host synchronisation.
+
+Parameter groups (`param_groups=`, torch.optim's list of dicts) and decoupled weight decay (`decoupled_weight_decay=`,
+`FusedAdamW`): up to 8 groups with their own `lr` / `weight_decay`, still one launch -- the byte per element that marks frozen
+parameters carries the group index (dyk_adam_step_groups / dyk_sgd_step_groups, csrc/optim.hip), and the groups' hyper-parameters
+travel as a kernel argument that is rebuilt from `param_groups` at every step, so LR schedulers and warm-up code that write
+`group['lr']` work as with torch.optim.  `yolo_param_groups(model, weight_decay)` builds the usual detector recipe: decay on
+weights of dimension >= 2 only.  One L2 group -- every caller that passes no groups -- takes the entries it always took.
 """
 import ctypes
+import struct
 
+import numpy as np
 import torch
 
 from . import lib as L
 from .lib import check, load
 
+MAX_GROUPS = L.OPT_MAX_GROUPS
+_SHARED_KEYS = ("betas", "eps", "momentum", "nesterov", "dampening")     # one value for all groups (DykOptimDesc carries them)
+
+
+def _fl32(x):
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
+def _entry_fields(e):
+    return (e.offset, e.numel, e.param) if hasattr(e, "offset") else e
+
+
+def group_map(entries, groups, total):
+    """The byte per element of the flat buffer that the grouped step kernels read: k on the elements of every parameter of
+    groups[k-1] that requires a gradient, 0 elsewhere (frozen parameters, parameters of no group, the padding behind every
+    entry).  entries: (offset, numel, param) records, or the ParamStore's entries; groups: dicts with 'params', as
+    optimizer.param_groups.  Entries start at multiples of 64 elements, so the four bytes of a 16-byte vector agree.
+    -> numpy uint8 array of `total` bytes"""
+    if not 1 <= len(groups) <= MAX_GROUPS:
+        raise ValueError("1 to %d parameter groups, got %d" % (MAX_GROUPS, len(groups)))
+    index = {}
+    for k, g in enumerate(groups, 1):
+        for p in g["params"]:
+            if id(p) in index:
+                raise ValueError("a parameter appears in more than one parameter group (groups %d and %d)" % (index[id(p)] - 1, k - 1))
+            index[id(p)] = k
+    out = np.zeros(total, np.uint8)
+    for e in entries:
+        off, n, p = _entry_fields(e)
+        if off % 4 or off < 0 or off + n > total:
+            raise ValueError("entry [%d, %d) does not fit a buffer of %d elements in whole 16-byte vectors" % (off, off + n, total))
+        if p.requires_grad:
+            out[off:off + n] = index.get(id(p), 0)
+    return out
+
+
+def yolo_param_groups(model, weight_decay, bias_lr=None):
+    """The three parameter groups of the YOLOv3/v4 training recipe over the trainable parameters of `model`:
+      0  weights of dimension >= 2 (convolution, depthwise, SE fully-connected): weight_decay
+      1  BatchNorm scale / shift and WeightedFeatureFusion.w: no decay
+      2  biases of every other module: no decay, `lr` = bias_lr when given (the warm-up schedule of the biases)
+    Frozen parameters (requires_grad False) are left out.  For FusedAdam / FusedSGD(param_groups=...) or torch.optim."""
+    import torch.nn as nn
+    decay, plain, biases = [], [], []
+    seen = set()
+    for mod in model.modules():
+        for name, p in mod.named_parameters(recurse=False):
+            if id(p) in seen or not p.requires_grad:
+                continue
+            seen.add(id(p))
+            if isinstance(mod, nn.modules.batchnorm._NormBase):
+                plain.append(p)
+            elif name == "bias":
+                biases.append(p)
+            elif p.dim() >= 2:
+                decay.append(p)
+            else:
+                plain.append(p)
+    groups = [dict(params=decay, weight_decay=float(weight_decay)), dict(params=plain, weight_decay=0.0),
+              dict(params=biases, weight_decay=0.0)]
+    if bias_lr is not None:
+        groups[2]["lr"] = float(bias_lr)
+    return groups
+
+
+def _checked_groups(model, param_groups, defaults):
+    """param_groups as torch.optim takes them, checked: at most 8, a partition of the trainable parameters of `model`, no
+    per-group value of a hyper-parameter the kernels share"""
+    groups = []
+    for g in param_groups:
+        if not isinstance(g, dict) or "params" not in g:
+            raise ValueError("param_groups must be a list of dicts with a 'params' entry")
+        ps = g["params"]
+        g = dict(g, params=[ps] if isinstance(ps, torch.Tensor) else list(ps))
+        for k in _SHARED_KEYS:
+            if k in g and k in defaults:
+                same = tuple(g[k]) == tuple(defaults[k]) if k == "betas" else g[k] == defaults[k]
+                if not same:
+                    raise ValueError("parameter groups share %r (%r); a group asks for %r" % (k, defaults[k], g[k]))
+        unknown = [k for k in g if k not in defaults and k != "params"]
+        if unknown:
+            raise ValueError("unknown parameter-group option(s) %s" % unknown)
+        groups.append(g)
+    if not 1 <= len(groups) <= MAX_GROUPS:
+        raise ValueError("1 to %d parameter groups, got %d" % (MAX_GROUPS, len(groups)))
+    names = {id(p): n for n, p in model.named_parameters()}
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    want = {id(p) for p in trainable}
+    seen = set()
+    for k, g in enumerate(groups):
+        for p in g["params"]:
+            if id(p) in seen:
+                raise ValueError("parameter %s appears in more than one parameter group" % names.get(id(p), "<not of this model>"))
+            if id(p) not in want:
+                raise ValueError("group %d holds %s, which is not a trainable parameter of the model" % (
+                    k, names.get(id(p), "a tensor")))
+            seen.add(id(p))
+    for p in trainable:
+        if id(p) not in seen:
+            raise ValueError("trainable parameter %s is in no parameter group" % names[id(p)])
+    return groups
+
 
 class _FusedBase(torch.optim.Optimizer):
     _state_names = ()            # torch.optim state entries that map onto the flat buffers (m, v)
 
-    def __init__(self, model, defaults, max_grad_norm=None, skip_nonfinite=False):
+    def __init__(self, model, defaults, max_grad_norm=None, skip_nonfinite=False, param_groups=None):
         if max_grad_norm is not None:
             max_grad_norm = float(max_grad_norm)
             if not (0.0 < max_grad_norm < float("inf")):
@@ -35,10 +146,12 @@ class _FusedBase(torch.optim.Optimizer):
         params = [p for p in model.parameters() if p.requires_grad]
         if not params:
             raise ValueError("optimizer got an empty parameter list")
-        super().__init__(params, defaults)
+        super().__init__(params if param_groups is None else _checked_groups(model, param_groups, defaults), defaults)
         self._t = 0
         self._m = self._v = None
         self._mask, self._mask_key = None, None
+        self._gmap, self._gmap_key = None, None      # grouped mode: the byte per element that names the group
+        self._step_mask = None                       # the mask the last _desc() handed to the kernel
         self.grad_scale = 1.0
         self.zero_in_step = True
         self._side = None
@@ -92,6 +205,30 @@ class _FusedBase(torch.optim.Optimizer):
                 self._mask = mask.to(st.P.device)
                 self._fresh = True
         return self._mask
+
+    def _grouped(self):
+        """more than one group, or decoupled decay: the `_groups` entries of the library.  One L2 group takes the entries, the
+        launches and the mask it always took."""
+        return len(self.param_groups) > 1 or any(g.get("decoupled_weight_decay", False) for g in self.param_groups)
+
+    def _group_map(self, st):
+        key = (st.frozen_key(), tuple(tuple(id(p) for p in g["params"]) for g in self.param_groups))
+        if key != self._gmap_key or self._gmap.device != st.P.device:
+            self._gmap_key = key
+            self._gmap = torch.from_numpy(group_map(st.entries, self.param_groups, st.total)).to(st.P.device)
+            self._fresh = True
+        return self._gmap
+
+    def _group_table(self):
+        """DykOptimGroups from param_groups as they are NOW (a scheduler may have written lr since the last step)"""
+        t = L.DykOptimGroups()
+        t.count = len(self.param_groups)
+        for k, g in enumerate(self.param_groups):
+            r = t.g[k]
+            r.lr, r.weight_decay = float(g["lr"]), float(g["weight_decay"])
+            r.decay_mul = _fl32(1.0 - _fl32(_fl32(r.lr) * _fl32(r.weight_decay)))
+            r.flags = L.OPT_GROUP_DECOUPLED if g.get("decoupled_weight_decay", False) else 0
+        return t
 
     def _take_buckets(self, works, total):
         """GradAllReduce.all_reduce(optimizer=self): [(work, lo, hi)] of the data-parallel exchange; accepted when the ranges tile
@@ -181,7 +318,12 @@ class _FusedBase(torch.optim.Optimizer):
         d.n = st.total
         d.lr, d.weight_decay, d.grad_scale = float(g["lr"]), float(g["weight_decay"]), float(self.grad_scale)
         d.zero_grad = 1 if self.zero_in_step else 0
-        mask = self._trainable_mask(st)
+        if self._grouped():
+            mask = self._group_map(st)               # (always there: the frozen-overwritten rule below applies)
+            d.lr = d.weight_decay = 0.0              # (ignored by the _groups entries: DykOptimGroups carries them)
+        else:
+            mask = self._trainable_mask(st)
+        self._step_mask = mask
         d.mask = mask.data_ptr() if mask is not None else None
         bf = st._compute.get(torch.bfloat16)
         d.wc = bf["Wc"].data_ptr() if bf is not None else None
@@ -219,7 +361,7 @@ class _FusedBase(torch.optim.Optimizer):
             for w, _, _ in buckets:
                 w.wait()
         rec = self._guard_record(st)
-        mask = self._mask                    # (_desc has refreshed it)
+        mask = self._step_mask               # (_desc has refreshed it; in grouped mode the group map: live = byte != 0)
         if self.skip_nonfinite:
             # a skipped step writes no bf16 copy at all: the cast may be left out only if the copy was current before the step
             self._wc_complete = bf is not None and bf["version"] == st.version_key()
@@ -294,12 +436,13 @@ class _FusedBase(torch.optim.Optimizer):
             return
         by_param = {id(e.param): e for e in st.entries}
         flats = dict(zip(self._state_names, (self._m, self._v)))
-        for p in self.param_groups[0]["params"]:
-            e = by_param[id(p)]
-            s = {"step": torch.tensor(float(self._t))}
-            for name, flat in flats.items():
-                s[name] = st._view(flat, e)
-            self.state[p] = s
+        for g in self.param_groups:
+            for p in g["params"]:
+                e = by_param[id(p)]
+                s = {"step": torch.tensor(float(self._t))}
+                for name, flat in flats.items():
+                    s[name] = st._view(flat, e)
+                self.state[p] = s
 
     def state_dict(self):
         if self._guarded and self._rec is not None:
@@ -308,7 +451,11 @@ class _FusedBase(torch.optim.Optimizer):
         return super().state_dict()
 
     def load_state_dict(self, state_dict):
+        decoupled = [g.get("decoupled_weight_decay") for g in self.param_groups]
         super().load_state_dict(state_dict)
+        for g, flag in zip(self.param_groups, decoupled):
+            if flag is not None:
+                g.setdefault("decoupled_weight_decay", flag)      # (a checkpoint of a torch without that option)
         st = self._store()
         m, v = self._buffers(st)
         flats = dict(zip(self._state_names, (m, v)))
@@ -340,8 +487,9 @@ class FusedAdam(_FusedBase):
     _state_names = ("exp_avg", "exp_avg_sq")
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
-                 skip_nonfinite=False):
-        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm, skip_nonfinite)
+                 skip_nonfinite=False, param_groups=None, decoupled_weight_decay=False):
+        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                     decoupled_weight_decay=bool(decoupled_weight_decay)), max_grad_norm, skip_nonfinite, param_groups)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -354,26 +502,42 @@ class FusedAdam(_FusedBase):
         d, bf = self._desc(st)
         g = self.param_groups[0]
         d.beta1, d.beta2, d.eps, d.step = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), self._t
-        self._launch(load().dyk_adam_step, "dyk_adam_step", d, bf)
+        if self._grouped():
+            table, fn = self._group_table(), load().dyk_adam_step_groups
+            self._launch(lambda dref, stream: fn(dref, ctypes.byref(table), None, stream), "dyk_adam_step_groups", d, bf)
+        else:
+            self._launch(load().dyk_adam_step, "dyk_adam_step", d, bf)
         self._finish(st, bf)
 
     def _step_guarded(self, st):
         d, bf = self._desc(st)
         g = self.param_groups[0]
         d.beta1, d.beta2, d.eps, d.step = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), 0
-        self._guarded_step(st, d, bf, load().dyk_adam_step_guarded, "dyk_adam_step_guarded", d.beta1, d.beta2)
+        if self._grouped():
+            table, fn = self._group_table(), load().dyk_adam_step_groups
+            self._guarded_step(st, d, bf, lambda dref, rp, stream: fn(dref, ctypes.byref(table), rp, stream),
+                               "dyk_adam_step_groups", d.beta1, d.beta2)
+        else:
+            self._guarded_step(st, d, bf, load().dyk_adam_step_guarded, "dyk_adam_step_guarded", d.beta1, d.beta2)
         self._finish(st, bf)
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW: FusedAdam with decoupled weight decay (p *= 1 - lr * weight_decay before the Adam update)"""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+        super().__init__(model, lr, betas, eps, weight_decay, decoupled_weight_decay=True, **kw)
 
 
 class FusedSGD(_FusedBase):
     _state_names = ("momentum_buffer",)
 
     def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=0.0, nesterov=True, max_grad_norm=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, param_groups=None):
         if not nesterov:
             raise NotImplementedError("the reference only uses nesterov=True (train.py:88-89)")
         super().__init__(model, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=True, dampening=0),
-                         max_grad_norm, skip_nonfinite)
+                         max_grad_norm, skip_nonfinite, param_groups)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -385,13 +549,22 @@ class FusedSGD(_FusedBase):
         self._t += 1
         d, bf = self._desc(st)
         d.beta1, d.step = float(self.param_groups[0]["momentum"]), self._t
-        self._launch(load().dyk_sgd_step, "dyk_sgd_step", d, bf)
+        if self._grouped():
+            table, fn = self._group_table(), load().dyk_sgd_step_groups
+            self._launch(lambda dref, stream: fn(dref, ctypes.byref(table), None, stream), "dyk_sgd_step_groups", d, bf)
+        else:
+            self._launch(load().dyk_sgd_step, "dyk_sgd_step", d, bf)
         self._finish(st, bf)
 
     def _step_guarded(self, st):
         d, bf = self._desc(st)
         d.beta1, d.step = float(self.param_groups[0]["momentum"]), 0
-        self._guarded_step(st, d, bf, load().dyk_sgd_step_guarded, "dyk_sgd_step_guarded", 0.0, 0.0)
+        if self._grouped():
+            table, fn = self._group_table(), load().dyk_sgd_step_groups
+            self._guarded_step(st, d, bf, lambda dref, rp, stream: fn(dref, ctypes.byref(table), rp, stream),
+                               "dyk_sgd_step_groups", 0.0, 0.0)
+        else:
+            self._guarded_step(st, d, bf, load().dyk_sgd_step_guarded, "dyk_sgd_step_guarded", 0.0, 0.0)
         self._finish(st, bf)
 
 

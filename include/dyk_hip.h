@@ -846,6 +846,52 @@ int dyk_sgd_step_guarded(const DykOptimDesc* desc, const DykGradGuardRec* rec, v
 int dyk_grad_scale_by_rec(float* g, const uint8_t* mask, int64_t n, const DykGradGuardRec* rec, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Parameter groups and decoupled weight decay for the fused optimizer steps (the YOLOv3/v4 recipe behind the reference's
+ * hyp.scratch*.json: weight decay on convolution weights only, a learning rate of their own for the biases during warm-up,
+ * AdamW), still one launch over the flat buffers.  The mask byte of DykOptimDesc carries the group:
+ *   0                          : frozen parameter or padding -- no update, no decay, moments untouched, g cleared when zero_grad
+ *                                is set (the meaning it has for dyk_adam_step / dyk_sgd_step)
+ *   k in 1..groups->count      : the element belongs to group k-1 and is updated with groups->g[k-1]
+ *   k > groups->count          : treated as 0 (frozen)
+ * Parameters start at multiples of 64 elements, so the four bytes of a 16-byte vector agree; the kernels read them as one
+ * 32-bit word and take its low byte.  "Live" keeps the meaning it has for dyk_grad_stats and dyk_grad_scale_by_rec (the four
+ * mask bytes not all 0): both take a group map as their mask unchanged.
+ * DykOptimGroups is passed to the kernel BY VALUE, as a kernel argument: a scheduler changes lr at every step, and a table in
+ * device memory would need a copy and an ordering edge per step.
+ *   lr, weight_decay : of the group; desc->lr and desc->weight_decay are ignored
+ *   flags bit 0      : DYK_OPT_GROUP_DECOUPLED, decoupled weight decay (torch.optim.AdamW): p = fl32(p * decay_mul) first, then
+ *                      the Adam statements with weight_decay = 0.  Without it: L2, the statements of dyk_adam_step / dyk_sgd_step
+ *                      with the group's lr and weight_decay.  Other bits must be 0.
+ *   decay_mul        : fl32(1 - fl32(lr * weight_decay)), formed by the caller; read for decoupled groups only
+ * beta1, beta2, eps (SGD: momentum in beta1), grad_scale, step, zero_grad and wc stay in DykOptimDesc and are shared by all
+ * groups.  The per-element statements are those of dyk_adam_step / dyk_sgd_step (one device function, csrc/optim_update.h): a
+ * group without the decoupled flag gets the bits dyk_adam_step / dyk_sgd_step give with that group's lr and weight_decay.
+ * dyk_adam_step_groups / dyk_sgd_step_groups(desc, groups, rec, stream):
+ *   rec == NULL : as dyk_adam_step / dyk_sgd_step -- bias corrections from desc->step (>= 1), SGD's first-step rule at step == 1
+ *   rec != NULL : as the _guarded entries -- rec->skip, grad_scale := fl32(desc->grad_scale * rec->coef), rec->bc1 /
+ *                 rec->bc2_sqrt, and the first-step rule at rec->applied == 1 (desc->step is ignored)
+ * The desc may name a sub-range (mask offset with it).  Before any launch: everything dyk_adam_step / dyk_sgd_step check, and
+ * mask not NULL and 4-byte aligned, 1 <= count <= DYK_OPT_MAX_GROUPS, every lr finite, every weight_decay >= 0, no unknown
+ * flag bit, rec 8-byte aligned; otherwise DYK_ERR_ARG and nothing is written.  A decoupled group handed to
+ * dyk_sgd_step_groups: DYK_ERR_UNSUPPORTED, nothing written.
+ * ---------------------------------------------------------------------------------- */
+#define DYK_OPT_MAX_GROUPS 8
+#define DYK_OPT_GROUP_DECOUPLED 1
+typedef struct DykOptimGroup {
+    float lr;
+    float weight_decay;
+    float decay_mul;
+    uint32_t flags;
+} DykOptimGroup;
+typedef struct DykOptimGroups {
+    int32_t count;
+    int32_t _pad[3];
+    DykOptimGroup g[DYK_OPT_MAX_GROUPS];
+} DykOptimGroups;
+int dyk_adam_step_groups(const DykOptimDesc* desc, const DykOptimGroups* groups, const DykGradGuardRec* rec_or_null, void* stream);
+int dyk_sgd_step_groups(const DykOptimDesc* desc, const DykOptimGroups* groups, const DykGradGuardRec* rec_or_null, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Exponential moving average of the flat buffers (replaces the per-entry loop of ModelEMA.update, reference
  * build_utils/torch_utils.py:108-120: `v *= d; v += (1. - d) * msd[k]` over every floating state_dict entry).
  * One launch for up to DYK_EMA_MAX_REGIONS regions (the parameter store P and the running statistics R):
