@@ -1,14 +1,13 @@
 // Non-finite guard and gradient clipping for the fused optimizers, decided on the device (what the reference harness gets from
 // amp.GradScaler, train_utils/kaist_train_eval_utils.py:44,103-108, and from torch.nn.utils.clip_grad_norm_): one fp64 reduction
 // over the flat gradient buffer in two launches (block partials, then one workgroup that folds them in block order and writes a
-// small record), and step kernels that take skip / clip coefficient / bias corrections from that record instead of from the
-// host.  No atomics and no in-launch hand-off: the kernel boundary orders the partials before the fold, and the fold before
-// the step.  HBM-bound: 16-byte vectors, four loads in flight per lane; per loaded float one fp32 product, one conversion and
-// one fp64 FMA (a few per cent of the fp64 vector rate at HBM speed).  The update statements are the device functions of
-// optim_update.h that adam_kernel / sgd_kernel of optim.hip inline too, so that an unclipped, unskipped step gives the same bits.
+// small record).  The step kernel of optim.hip takes skip / clip coefficient / bias corrections from that record instead of
+// from the host; dyk_grad_scale_by_rec applies the coefficient to the gradient for users of stock torch.optim.  No atomics and no
+// in-launch hand-off: the kernel boundary orders the partials before the fold, and the fold before the step.  HBM-bound: 16-byte
+// vectors, four loads in flight per lane; per loaded float one fp32 product, one conversion and one fp64 FMA (a few per cent of
+// the fp64 vector rate at HBM speed).
 #include <float.h>
 #include "dyk_common.h"
-#include "optim_update.h"
 
 namespace {
 
@@ -153,50 +152,6 @@ __global__ __launch_bounds__(kBlock) void stats_finalize_kernel(const GradPartia
     }
 }
 
-__device__ __forceinline__ void clear_grads(const DykOptimDesc& d) {
-    const long n4 = d.n >> 2;
-    if (!d.zero_grad) return;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
-        ((float4*)d.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// adam_kernel of optim.hip with skip / grad_scale / bias corrections from the record: the same device function per vector
-__global__ __launch_bounds__(256) void adam_guarded_kernel(DykOptimDesc d, const DykGradGuardRec* __restrict__ rec) {
-    if (rec->skip) {
-        clear_grads(d);
-        return;
-    }
-    const float bc1 = rec->bc1, bc2_sqrt = rec->bc2_sqrt;
-    const long n4 = d.n >> 2;
-    const float lr = d.lr, b1 = d.beta1, b2 = d.beta2, eps = d.eps, wd = d.weight_decay, gs = __fmul_rn(d.grad_scale, rec->coef);
-    const float step_size = lr / bc1;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        if (d.mask && ((const uint32_t*)d.mask)[i] == 0) {      // frozen parameters (entries are 64-element aligned)
-            dyk_optim::clear_grad_vec(d, i);
-            continue;
-        }
-        dyk_optim::adam_vec(d, i, gs, wd, b1, b2, eps, bc2_sqrt, step_size, false, 1.f);
-    }
-}
-
-// sgd_kernel of optim.hip; the first-step rule fires at the first APPLIED step
-__global__ __launch_bounds__(256) void sgd_guarded_kernel(DykOptimDesc d, const DykGradGuardRec* __restrict__ rec) {
-    if (rec->skip) {
-        clear_grads(d);
-        return;
-    }
-    const int first_step = rec->applied == 1 ? 1 : 0;
-    const long n4 = d.n >> 2;
-    const float lr = d.lr, mom = d.beta1, wd = d.weight_decay, gs = __fmul_rn(d.grad_scale, rec->coef);
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        if (d.mask && ((const uint32_t*)d.mask)[i] == 0) {
-            dyk_optim::clear_grad_vec(d, i);
-            continue;
-        }
-        dyk_optim::sgd_vec(d, i, gs, wd, mom, lr, first_step);
-    }
-}
-
 __global__ __launch_bounds__(256) void scale_by_rec_kernel(float4* __restrict__ g, const uint32_t* __restrict__ mask, long n4,
                                                            const DykGradGuardRec* __restrict__ rec) {
     const float coef = rec->coef;
@@ -210,21 +165,6 @@ __global__ __launch_bounds__(256) void scale_by_rec_kernel(float4* __restrict__ 
         v.w = __fmul_rn(v.w, coef);
         g[i] = v;
     }
-}
-
-// the checks of optim.hip's entries, plus the record
-int check_step(const DykOptimDesc* d, const DykGradGuardRec* rec, bool need_v) {
-    if (!d || !rec || !d->p || !d->g || !d->m || (need_v && !d->v) || d->n <= 0 || (d->n & 3)) return DYK_ERR_ARG;
-    if (((uintptr_t)d->p | (uintptr_t)d->g | (uintptr_t)d->m | (uintptr_t)d->v) & 15) return DYK_ERR_ARG;
-    if (d->wc && ((uintptr_t)d->wc & 7)) return DYK_ERR_ARG;
-    if (d->mask && ((uintptr_t)d->mask & 3)) return DYK_ERR_ARG;
-    if ((uintptr_t)rec & 7) return DYK_ERR_ARG;
-    return DYK_OK;
-}
-
-long step_grid(long n) {
-    long g = ((n >> 2) + 255) / 256;
-    return g > 8192 ? 8192 : g;
 }
 
 }  // namespace
@@ -256,26 +196,11 @@ extern "C" int dyk_grad_stats(const DykGradStatsDesc* d, void* stream) {
     return DYK_OK;
 }
 
-extern "C" int dyk_adam_step_guarded(const DykOptimDesc* d, const DykGradGuardRec* rec, void* stream) {
-    const int rc = check_step(d, rec, true);
-    if (rc) return rc;
-    hipLaunchKernelGGL(adam_guarded_kernel, dim3((int)step_grid(d->n)), dim3(256), 0, (hipStream_t)stream, *d, rec);
-    DYK_LAUNCH_CHECK();
-    return DYK_OK;
-}
-
-extern "C" int dyk_sgd_step_guarded(const DykOptimDesc* d, const DykGradGuardRec* rec, void* stream) {
-    const int rc = check_step(d, rec, false);
-    if (rc) return rc;
-    hipLaunchKernelGGL(sgd_guarded_kernel, dim3((int)step_grid(d->n)), dim3(256), 0, (hipStream_t)stream, *d, rec);
-    DYK_LAUNCH_CHECK();
-    return DYK_OK;
-}
-
 extern "C" int dyk_grad_scale_by_rec(float* g, const uint8_t* mask, int64_t n, const DykGradGuardRec* rec, void* stream) {
     if (!g || !rec || n <= 0 || (n & 3)) return DYK_ERR_ARG;
     if (((uintptr_t)g & 15) || ((uintptr_t)rec & 7) || (mask && ((uintptr_t)mask & 3))) return DYK_ERR_ARG;
-    hipLaunchKernelGGL(scale_by_rec_kernel, dim3((int)step_grid(n)), dim3(256), 0, (hipStream_t)stream, (float4*)g,
+    const long blocks = ((n >> 2) + 255) / 256;
+    hipLaunchKernelGGL(scale_by_rec_kernel, dim3((int)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, (hipStream_t)stream, (float4*)g,
                        (const uint32_t*)mask, (long)(n >> 2), rec);
     DYK_LAUNCH_CHECK();
     return DYK_OK;

@@ -348,7 +348,7 @@ def bn_finalize(stats, count, gamma, beta, running_mean, running_var, momentum=0
     return scale, shift, mean, rstd
 
 
-# --------------------------------------------------------------------------- gradient guard (csrc/optim_guard.hip)
+# --------------------------------------------------------------------------- gradient guard (csrc/optim_guard.hip, csrc/optim.hip)
 GRAD_REC_BYTES = ctypes.sizeof(_l.DykGradGuardRec)
 
 
@@ -384,13 +384,17 @@ def grad_stats(g, rec, ws, *, mask=None, grad_scale=1.0, max_norm=0.0, beta1=0.0
     call("dyk_grad_stats", d)
 
 
+def _step_guarded(name, desc, rec):
+    check(getattr(load(), name)(ctypes.byref(desc), _ptr(rec), _stream()), name)
+
+
 def adam_step_guarded(desc, rec):
     """dyk_adam_step on the DykOptimDesc `desc`, with skip / clip coefficient / bias corrections from the record"""
-    check(load().dyk_adam_step_guarded(ctypes.byref(desc), _ptr(rec), _stream()), "dyk_adam_step_guarded")
+    _step_guarded("dyk_adam_step_guarded", desc, rec)
 
 
 def sgd_step_guarded(desc, rec):
-    check(load().dyk_sgd_step_guarded(ctypes.byref(desc), _ptr(rec), _stream()), "dyk_sgd_step_guarded")
+    _step_guarded("dyk_sgd_step_guarded", desc, rec)
 
 
 def grad_scale_by_rec(g, rec, mask=None, n=None):

@@ -8,7 +8,9 @@ rule, same constructor arguments, `step()` / `zero_grad()` / `param_groups[0]['l
 
 Opt-in protection (`max_grad_norm=`, `skip_nonfinite=`): what the reference harness gets from amp.GradScaler
 (train_utils/kaist_train_eval_utils.py:44,103-108) and torch.nn.utils.clip_grad_norm_, decided on the device from one
-reduction over the flat gradient buffer (csrc/optim_guard.hip) -- no per-tensor kernels, no host synchronisation.
+reduction over the flat gradient buffer (csrc/optim_guard.hip) -- no per-tensor kernels, no host synchronisation.  The step
+reads the decision from a small device record; FusedAdam and FusedSGD share one step() that picks the library entry from
+(update rule, parameter groups or not, record or not).
 
 Parameter groups (`param_groups=`, torch.optim's list of dicts) and decoupled weight decay (`decoupled_weight_decay=`,
 `FusedAdamW`): up to 8 groups with their own `lr` / `weight_decay`, still one launch -- the byte per element that marks frozen
@@ -18,6 +20,7 @@ travel as a kernel argument that is rebuilt from `param_groups` at every step, s
 weights of dimension >= 2 only.  One L2 group -- every caller that passes no groups -- takes the entries it always took.
 """
 import ctypes
+import os
 import struct
 
 import numpy as np
@@ -60,6 +63,21 @@ def group_map(entries, groups, total):
         if p.requires_grad:
             out[off:off + n] = index.get(id(p), 0)
     return out
+
+
+def trainable_mask(st):
+    """None when every parameter of the store is trainable, else a byte per element of the flat buffer on its device (1 = update):
+    frozen parameters get neither the update nor weight decay nor moments -- group_map with the trainable parameters as one group"""
+    if not st.frozen_key():
+        return None
+    live = [dict(params=[e.param for e in st.entries if e.param.requires_grad])]
+    return torch.from_numpy(group_map(st.entries, live, st.total)).to(st.P.device)
+
+
+def _rec_field(rec, name, dtype):
+    """one field of a DykGradGuardRec held as device bytes, as a one-element tensor view"""
+    f = getattr(L.DykGradGuardRec, name)
+    return rec[f.offset:f.offset + f.size].view(dtype)
 
 
 def yolo_param_groups(model, weight_decay, bias_lr=None):
@@ -131,6 +149,11 @@ def _checked_groups(model, param_groups, defaults):
 
 class _FusedBase(torch.optim.Optimizer):
     _state_names = ()            # torch.optim state entries that map onto the flat buffers (m, v)
+    _rule = None                 # "adam" / "sgd": the library entries are dyk_<rule>_step, ..._guarded, ..._groups
+
+    def _hyper(self, d):
+        """writes the rule's shared hyper-parameters into the DykOptimDesc `d` -> (beta1, beta2) of the record's bias corrections"""
+        raise NotImplementedError
 
     def __init__(self, model, defaults, max_grad_norm=None, skip_nonfinite=False, param_groups=None):
         if max_grad_norm is not None:
@@ -157,7 +180,6 @@ class _FusedBase(torch.optim.Optimizer):
         self._side = None
         self._buckets = None
         self._fresh = True
-        import os
         mode = os.environ.get("DYK_OPT_OVERLAP", "1")
         self.early_start = mode == "early"
         if mode != "0":
@@ -195,14 +217,8 @@ class _FusedBase(torch.optim.Optimizer):
         key = st.frozen_key()
         if key != self._mask_key:
             self._mask_key = key
-            if not key:
-                self._mask = None
-            else:
-                mask = torch.zeros(st.total, dtype=torch.uint8)
-                for e in st.entries:
-                    if e.param.requires_grad:
-                        mask[e.offset:e.offset + e.numel] = 1
-                self._mask = mask.to(st.P.device)
+            self._mask = trainable_mask(st)
+            if self._mask is not None:
                 self._fresh = True
         return self._mask
 
@@ -240,14 +256,14 @@ class _FusedBase(torch.optim.Optimizer):
         self._buckets = list(works)
         return True
 
-    def _launch(self, fn, name, d, bf):
+    def _launch(self, fn, name, d, buckets, wait_for_main):
         """one launch over the whole flat buffer -- or, when the last backward left an event behind its first segment
         (engine._early: gradients of G[lo:] final, single GPU), two: [lo, total) on a side stream as soon as that event has
-        passed, [0, lo) behind the backward on the caller's stream, which then waits for the side stream.  Same arithmetic per
-        element; the 0.66 ms HBM-bound step of the target cfg no longer runs alone after the backward's tail."""
+        passed (wait_for_main: as soon as everything the caller has enqueued has), [0, lo) behind the backward on the caller's
+        stream, which then waits for the side stream.  Same arithmetic per element; the 0.66 ms HBM-bound step of the target cfg
+        no longer runs alone after the backward's tail.  buckets: those of _take_buckets, or None."""
         eng = self.model.engine
         early, eng._early = eng._early, None
-        buckets, self._buckets = self._buckets, None
         main = torch.cuda.current_stream()
         if buckets is None and (early is None or self.model.engine.grad_sync is not None):
             check(fn(ctypes.byref(d), ctypes.c_void_p(main.cuda_stream)), name)
@@ -291,7 +307,7 @@ class _FusedBase(torch.optim.Optimizer):
             main.wait_event(done)
             return
         ev, lo = early
-        if self.early_start and ev is not None:
+        if not wait_for_main and ev is not None:
             # opt-in (DYK_OPT_OVERLAP=early / optimizer.early_start = True): the side stream waits for the event recorded in the
             # MIDDLE of the backward pass only.  Anything the caller enqueued on its own stream between backward() and step() that
             # touches gradients -- clip_grad_norm_, manual scaling, gradient-norm logging -- is NOT ordered against it (a clip
@@ -334,8 +350,6 @@ class _FusedBase(torch.optim.Optimizer):
         return d, bf
 
     # ------------------------------------------------------------------ guarded mode (max_grad_norm / skip_nonfinite)
-    _REC_APPLIED = 6             # int32 index of DykGradGuardRec.applied (include/dyk_hip.h)
-
     def _guard_record(self, st):
         if self._rec is None or self._rec.device != st.P.device:
             from . import ops
@@ -345,35 +359,61 @@ class _FusedBase(torch.optim.Optimizer):
             self._stats_ws = ops.grad_stats_workspace(st.total, st.P.device)
             self._stats_ring = [torch.zeros(8, ops.GRAD_REC_BYTES, dtype=torch.uint8).pin_memory(), 0]
             if self._t:                      # a checkpoint was loaded before the first step
-                self._rec.view(torch.int32)[self._REC_APPLIED] = self._t
+                _rec_field(self._rec, "applied", torch.int32)[0] = self._t
             self._fresh = True
         return self._rec
 
-    def _guarded_step(self, st, d, bf, step_fn, name, beta1, beta2):
-        """dyk_grad_stats over the whole G on the caller's stream (behind everything enqueued so far: the backward, a
-        data-parallel all-reduce), the record's asynchronous copy to pinned memory, then the guarded step -- one launch or the
-        two ranges of _launch, both reading the same record.  With data-parallel buckets the norm needs all of G: the caller's
-        stream waits for every bucket first and the bucket-wise overlap is given up (every rank holds the same G afterwards
-        and reaches the same decision without a further collective)."""
+    def _decide(self, st, d, bf, betas, buckets):
+        """guarded mode, before the step: dyk_grad_stats over the whole G on the caller's stream (behind everything enqueued so
+        far: the backward, a data-parallel all-reduce) and the record's asynchronous copy to pinned memory -> the record, which
+        the step -- one launch or the two ranges of _launch -- reads.  With data-parallel buckets the norm needs all of G: the
+        caller's stream waits for every bucket first and the bucket-wise overlap is given up (every rank holds the same G
+        afterwards and reaches the same decision without a further collective)."""
         from . import ops
-        buckets, self._buckets = self._buckets, None
-        if buckets is not None:
-            for w, _, _ in buckets:
-                w.wait()
+        for w, _, _ in buckets or ():
+            w.wait()
         rec = self._guard_record(st)
-        mask = self._step_mask               # (_desc has refreshed it; in grouped mode the group map: live = byte != 0)
         if self.skip_nonfinite:
             # a skipped step writes no bf16 copy at all: the cast may be left out only if the copy was current before the step
             self._wc_complete = bf is not None and bf["version"] == st.version_key()
-        ops.grad_stats(st.G, rec, self._stats_ws, mask=mask, grad_scale=d.grad_scale, max_norm=self.max_grad_norm or 0.0,
-                       beta1=beta1, beta2=beta2, skip_nonfinite=self.skip_nonfinite)
+        # (_desc has refreshed _step_mask; in grouped mode it is the group map: live = byte != 0)
+        ops.grad_stats(st.G, rec, self._stats_ws, mask=self._step_mask, grad_scale=d.grad_scale, max_norm=self.max_grad_norm or 0.0,
+                       beta1=betas[0], beta2=betas[1], skip_nonfinite=self.skip_nonfinite)
         self._publish_stats(rec)
-        early_start, self.early_start = self.early_start, False     # (the side stream must wait for the statistics)
-        try:
-            rp = ctypes.c_void_p(rec.data_ptr())
-            self._launch(lambda dref, stream: step_fn(dref, rp, stream), name, d, bf)
-        finally:
-            self.early_start = early_start
+        return rec
+
+    def _entry(self, rec):
+        """the library entry of (rule, grouped, with a record) with the group table and the record bound
+        -> (callable(descriptor reference, stream), its name for `check`)"""
+        grouped = self._grouped()
+        name = "dyk_%s_step%s" % (self._rule, "_groups" if grouped else "_guarded" if rec is not None else "")
+        fn = getattr(load(), name)
+        rp = ctypes.c_void_p(rec.data_ptr()) if rec is not None else None
+        if grouped:
+            table = self._group_table()
+            return (lambda dref, stream: fn(dref, ctypes.byref(table), rp, stream)), name
+        if rec is not None:
+            return (lambda dref, stream: fn(dref, rp, stream)), name
+        return fn, name
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        st = self._store()
+        self._check_loss_flag()
+        st.attach_grads()
+        if not self._guarded:                # (guarded: the record counts the steps that were applied)
+            self._t += 1
+        d, bf = self._desc(st)
+        betas = self._hyper(d)
+        d.step = 0 if self._guarded else self._t
+        buckets, self._buckets = self._buckets, None
+        rec = None
+        if self._guarded:
+            rec, buckets = self._decide(st, d, bf, betas, buckets), None
+        fn, name = self._entry(rec)
+        # (with a record the side stream must wait for the statistics, which run on the caller's stream)
+        self._launch(fn, name, d, buckets, wait_for_main=rec is not None or not self.early_start)
+        self._finish(st, bf)
 
     def _publish_stats(self, rec):
         ring, pend = self._stats_ring, self._stats_pending
@@ -478,48 +518,24 @@ class _FusedBase(torch.optim.Optimizer):
         self._t = steps.pop() if steps else (1 if loaded else 0)
         if self._rec is not None:
             self.grad_stats(wait=True)       # (copies of earlier steps must not overwrite _t afterwards)
-            self._rec.view(torch.int32)[self._REC_APPLIED] = self._t
+            _rec_field(self._rec, "applied", torch.int32)[0] = self._t
         self.state.clear()               # the flat buffers are the state; views are rebuilt on demand
         self._fresh = True               # (the copies above ran on the caller's stream)
 
 
 class FusedAdam(_FusedBase):
     _state_names = ("exp_avg", "exp_avg_sq")
+    _rule = "adam"
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
                  skip_nonfinite=False, param_groups=None, decoupled_weight_decay=False):
         super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                      decoupled_weight_decay=bool(decoupled_weight_decay)), max_grad_norm, skip_nonfinite, param_groups)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        st = self._store()
-        self._check_loss_flag()
-        st.attach_grads()
-        if self._guarded:
-            return self._step_guarded(st)
-        self._t += 1
-        d, bf = self._desc(st)
+    def _hyper(self, d):
         g = self.param_groups[0]
-        d.beta1, d.beta2, d.eps, d.step = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), self._t
-        if self._grouped():
-            table, fn = self._group_table(), load().dyk_adam_step_groups
-            self._launch(lambda dref, stream: fn(dref, ctypes.byref(table), None, stream), "dyk_adam_step_groups", d, bf)
-        else:
-            self._launch(load().dyk_adam_step, "dyk_adam_step", d, bf)
-        self._finish(st, bf)
-
-    def _step_guarded(self, st):
-        d, bf = self._desc(st)
-        g = self.param_groups[0]
-        d.beta1, d.beta2, d.eps, d.step = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), 0
-        if self._grouped():
-            table, fn = self._group_table(), load().dyk_adam_step_groups
-            self._guarded_step(st, d, bf, lambda dref, rp, stream: fn(dref, ctypes.byref(table), rp, stream),
-                               "dyk_adam_step_groups", d.beta1, d.beta2)
-        else:
-            self._guarded_step(st, d, bf, load().dyk_adam_step_guarded, "dyk_adam_step_guarded", d.beta1, d.beta2)
-        self._finish(st, bf)
+        d.beta1, d.beta2, d.eps = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+        return d.beta1, d.beta2
 
 
 class FusedAdamW(FusedAdam):
@@ -531,6 +547,7 @@ class FusedAdamW(FusedAdam):
 
 class FusedSGD(_FusedBase):
     _state_names = ("momentum_buffer",)
+    _rule = "sgd"
 
     def __init__(self, model, lr=1e-3, momentum=0.9, weight_decay=0.0, nesterov=True, max_grad_norm=None,
                  skip_nonfinite=False, param_groups=None):
@@ -539,33 +556,9 @@ class FusedSGD(_FusedBase):
         super().__init__(model, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=True, dampening=0),
                          max_grad_norm, skip_nonfinite, param_groups)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        st = self._store()
-        self._check_loss_flag()
-        st.attach_grads()
-        if self._guarded:
-            return self._step_guarded(st)
-        self._t += 1
-        d, bf = self._desc(st)
-        d.beta1, d.step = float(self.param_groups[0]["momentum"]), self._t
-        if self._grouped():
-            table, fn = self._group_table(), load().dyk_sgd_step_groups
-            self._launch(lambda dref, stream: fn(dref, ctypes.byref(table), None, stream), "dyk_sgd_step_groups", d, bf)
-        else:
-            self._launch(load().dyk_sgd_step, "dyk_sgd_step", d, bf)
-        self._finish(st, bf)
-
-    def _step_guarded(self, st):
-        d, bf = self._desc(st)
-        d.beta1, d.step = float(self.param_groups[0]["momentum"]), 0
-        if self._grouped():
-            table, fn = self._group_table(), load().dyk_sgd_step_groups
-            self._guarded_step(st, d, bf, lambda dref, rp, stream: fn(dref, ctypes.byref(table), rp, stream),
-                               "dyk_sgd_step_groups", 0.0, 0.0)
-        else:
-            self._guarded_step(st, d, bf, load().dyk_sgd_step_guarded, "dyk_sgd_step_guarded", 0.0, 0.0)
-        self._finish(st, bf)
+    def _hyper(self, d):
+        d.beta1 = float(self.param_groups[0]["momentum"])
+        return 0.0, 0.0
 
 
 def clip_grad_norm_(model, max_norm, norm_type=2.0):
@@ -588,16 +581,9 @@ def clip_grad_norm_(model, max_norm, norm_type=2.0):
     state = m.__dict__.get("_dyk_clip")
     key = (st.frozen_key(), st.P.device)
     if state is None or state["key"] != key:
-        mask = None
-        if key[0]:
-            mask = torch.zeros(st.total, dtype=torch.uint8)
-            for e in st.entries:
-                if e.param.requires_grad:
-                    mask[e.offset:e.offset + e.numel] = 1
-            mask = mask.to(st.P.device)
-        state = m.__dict__["_dyk_clip"] = dict(key=key, mask=mask, rec=ops.grad_guard_record(st.P.device),
+        state = m.__dict__["_dyk_clip"] = dict(key=key, mask=trainable_mask(st), rec=ops.grad_guard_record(st.P.device),
                                                ws=ops.grad_stats_workspace(st.total, st.P.device))
     rec, mask = state["rec"], state["mask"]
     ops.grad_stats(st.G, rec, state["ws"], mask=mask, max_norm=max_norm)
     ops.grad_scale_by_rec(st.G, rec, mask=mask)
-    return rec[8:12].view(torch.float32)[0].clone()
+    return _rec_field(rec, "norm", torch.float32)[0].clone()

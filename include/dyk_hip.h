@@ -864,7 +864,7 @@ int dyk_grad_scale_by_rec(float* g, const uint8_t* mask, int64_t n, const DykGra
  *                      with the group's lr and weight_decay.  Other bits must be 0.
  *   decay_mul        : fl32(1 - fl32(lr * weight_decay)), formed by the caller; read for decoupled groups only
  * beta1, beta2, eps (SGD: momentum in beta1), grad_scale, step, zero_grad and wc stay in DykOptimDesc and are shared by all
- * groups.  The per-element statements are those of dyk_adam_step / dyk_sgd_step (one device function, csrc/optim_update.h): a
+ * groups.  The per-element statements are those of dyk_adam_step / dyk_sgd_step (one device function, csrc/optim.hip): a
  * group without the decoupled flag gets the bits dyk_adam_step / dyk_sgd_step give with that group's lr and weight_decay.
  * dyk_adam_step_groups / dyk_sgd_step_groups(desc, groups, rec, stream):
  *   rec == NULL : as dyk_adam_step / dyk_sgd_step -- bias corrections from desc->step (>= 1), SGD's first-step rule at step == 1

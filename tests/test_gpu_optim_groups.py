@@ -194,7 +194,7 @@ def test_a_byte_above_the_count_is_frozen():
     assert np.all(b.bits("wc")[gmap > 2] == 0x1234) and not b.bits("g").any()
 
 
-# ------------------------------------------------------------------ the same bits as the existing kernels
+# ------------------------------------------------------------------ the same bits as the plain and the _guarded entries
 @pytest.mark.parametrize("name", ["interleaved", "big"])
 @pytest.mark.parametrize("with_rec", [False, True])
 @pytest.mark.parametrize("kind", ["adam", "sgd"])
@@ -219,8 +219,9 @@ def test_equal_groups_give_the_bits_of_the_existing_kernels(kind, with_rec, name
 @pytest.mark.parametrize("with_rec", [False, True])
 @pytest.mark.parametrize("kind", ["adam", "sgd"])
 def test_every_l2_group_of_a_mixed_launch_has_the_bits_of_the_existing_kernel(kind, with_rec):
-    """group k of ONE mixed launch == the existing kernel launched with group k's lr / weight_decay and a mask that keeps group k
-    only (the kernels share one device function).  The decoupled group has no counterpart; it must leave the others alone."""
+    """group k of ONE mixed launch == the plain (with a record: the _guarded) entry launched with group k's lr / weight_decay and a
+    mask that keeps group k only (one kernel template behind all entries: this is the ABI's contract).  The decoupled group has no
+    counterpart; it must leave the others alone."""
     n, gmap, groups = layout("interleaved", kind)
     for step in (1, 1000):
         h = hyper(kind, step, 1 / 8)

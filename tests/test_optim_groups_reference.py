@@ -27,7 +27,7 @@ def groups_of(kind):
 
 # ------------------------------------------------------------------ fp32 emulation of the grouped kernels
 def emulate(kind, p, g, m, v, gmap, groups, *, beta1, beta2=0.0, eps=0.0, grad_scale=1.0, step=1, table=None, late_decay=False):
-    """numpy float32, one rounding per operation, in the statement order of csrc/optim_update.h.  `table` replaces
+    """numpy float32, one rounding per operation, in the statement order of adam_vec / sgd_vec (csrc/optim.hip).  `table` replaces
     optim_groups_ref.table(groups) (the mutants hand in a confused one); late_decay applies decay_mul after the update."""
     p1, m1, v1 = p.copy(), m.copy(), v.copy()
     for k, (lr, wd, dm, flags) in enumerate(R.table(groups) if table is None else table, 1):

@@ -32,8 +32,8 @@ def collect(d):
                 rows.append((int(r["Dispatch_Id"]), family(r["Kernel_Name"]), r["Counter_Name"], float(r["Counter_Value"]), int(r.get("Grid_Size", 0) or 0)))
     rows.sort()
     # round 4: two optimizer launches per step, enqueued back to back: a step ends with the SMALLER one
-    grids = sorted({r[4] for r in rows if r[1] in ("adam_kernel", "sgd_kernel")})
-    ids = sorted({r[0] for r in rows if r[1] in ("adam_kernel", "sgd_kernel") and (len(grids) < 2 or r[4] == grids[0])})
+    grids = sorted({r[4] for r in rows if r[1] in ("step_kernel", "adam_kernel", "sgd_kernel")})
+    ids = sorted({r[0] for r in rows if r[1] in ("step_kernel", "adam_kernel", "sgd_kernel") and (len(grids) < 2 or r[4] == grids[0])})
     rows = [r[:4] for r in rows]
     lo, hi = (ids[-2], ids[-1]) if len(ids) >= 2 else (-1, 1 << 62)
     out = {}

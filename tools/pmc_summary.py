@@ -23,7 +23,7 @@ def collect(d, counter):
         with open(path) as f:
             rows += [r for r in csv.DictReader(f) if r.get("Counter_Name") == counter]
     rows.sort(key=lambda r: int(r["Dispatch_Id"]))
-    opt = [r for r in rows if family(r["Kernel_Name"]) in ("adam_kernel", "sgd_kernel")]
+    opt = [r for r in rows if family(r["Kernel_Name"]) in ("step_kernel", "adam_kernel", "sgd_kernel")]
     # round 4: two optimizer launches per step (deep layers on a side stream, the rest behind the backward; enqueued back to back):
     # a step ends with the SMALLER one
     grids = sorted({int(r.get("Grid_Size", 0) or 0) for r in opt})

@@ -18,7 +18,7 @@ def family(name):
 def main():
     rows = list(csv.DictReader(open(sys.argv[1])))
     ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r["Stream_Id"], int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0)) for r in rows)
-    opt = [i for i, e in enumerate(ev) if "adam_kernel" in e[2] or "sgd_kernel" in e[2]]
+    opt = [i for i, e in enumerate(ev) if any(k in e[2] for k in ("::step_kernel<", "adam_kernel", "sgd_kernel"))]
     # round 4: two optimizer launches per step (deep layers early on a side stream, the rest behind the backward): the step
     # ends with the SMALLER one
     grids = sorted({ev[i][4] for i in opt})

@@ -11,7 +11,7 @@ import sys
 _f = io.TextIOWrapper(gzip.open(sys.argv[1])) if sys.argv[1].endswith(".gz") else open(sys.argv[1])
 rows = list(csv.DictReader(_f))
 ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r["Stream_Id"], int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0)) for r in rows)
-adam = [i for i, e in enumerate(ev) if "adam_kernel" in e[2] or "sgd_kernel" in e[2]]
+adam = [i for i, e in enumerate(ev) if any(k in e[2] for k in ("::step_kernel<", "adam_kernel", "sgd_kernel"))]
 # round 4: the optimizer runs as two launches per step (deep layers early on a side stream, the rest behind the backward):
 # the step ends with the SMALLER one
 grids = sorted({ev[i][4] for i in adam})

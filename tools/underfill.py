@@ -7,7 +7,7 @@ path = sys.argv[1]
 f = io.TextIOWrapper(gzip.open(path)) if path.endswith(".gz") else open(path)
 rows = [r for r in csv.DictReader(f)]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-opt = [i for i, r in enumerate(rows) if "adam_kernel" in r["Kernel_Name"] or "sgd_kernel" in r["Kernel_Name"]]
+opt = [i for i, r in enumerate(rows) if any(k in r["Kernel_Name"] for k in ("::step_kernel<", "adam_kernel", "sgd_kernel"))]
 starts = [opt[0]] + [b for a, b in zip(opt, opt[1:]) if int(rows[b]["Start_Timestamp"]) - int(rows[a]["Start_Timestamp"]) > 2_000_000]
 lo, hi = starts[-2], starts[-1]
 step = rows[lo:hi]
