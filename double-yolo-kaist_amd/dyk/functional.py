@@ -139,8 +139,7 @@ def conv_bn_act(x, conv, bn, act, training):
 def maxpool(x, k, stride=1):
     xd = _nhwc(x)
     B, H, W, C = xd.shape
-    pad = (k - 1) // 2
-    z = torch.empty((B, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1, C), dtype=xd.dtype, device=xd.device)
+    z = torch.empty((B, ops.maxpool_out_size(H, k, stride), ops.maxpool_out_size(W, k, stride), C), dtype=xd.dtype, device=xd.device)
     d = ops.ew_desc(a=xd, out=z, B=B, H=H, W=W, k=k)
     d.slots = stride
     ops.call("dyk_maxpool_fwd", d, None)

@@ -94,6 +94,18 @@ def conv_out_size(n, k, stride, pad):
     return (n + 2 * pad - k) // stride + 1
 
 
+def maxpool_out_size(n, k, stride):
+    """Output extent of nn.MaxPool2d(k, stride, padding=(k-1)//2) over n pixels.  A map smaller than the unpadded part of the
+    window (n + 2 pad - k < 0: an even window on one pixel) has no output and torch refuses it; so does this.  The pool kernels
+    compute the extent themselves, (n + 2 pad - k) / stride + 1 truncated towards zero, which makes that ONE output at stride
+    >= 2: with the empty tensor a caller allocates for it they would write past its end, so every caller sizes its output
+    here, before anything is allocated or launched."""
+    m = n + 2 * ((k - 1) // 2) - k
+    if m < 0:
+        raise ValueError("max pool %d x %d over %d pixels has no output" % (k, k, n))
+    return m // stride + 1
+
+
 def fwd_taps(k, pad):
     """(tdy, tdx, twt) of a k x k forward convolution with zero padding `pad`."""
     taps = []

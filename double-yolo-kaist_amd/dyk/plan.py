@@ -18,7 +18,7 @@ import os
 import torch
 
 from . import lib as L
-from .ops import conv_out_size, dgrad_classes, fwd_taps
+from .ops import conv_out_size, dgrad_classes, fwd_taps, maxpool_out_size
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 HEAD_LD = 32            # head conv outputs / their gradients live in 32-channel rows
@@ -896,8 +896,8 @@ def _emit_forward(cx):
             k, stride = m["size"], m["stride"]
             if not (1 <= k <= 15 and 1 <= stride <= 8):
                 raise NotImplementedError("[maxpool] size %s stride %s" % (k, stride))
-            mp = (k - 1) // 2                                   # nn.MaxPool2d(k, stride, padding=(k-1)//2), models.py:91-94
-            Hp, Wp = (x_in.H + 2 * mp - k) // stride + 1, (x_in.W + 2 * mp - k) // stride + 1
+            # nn.MaxPool2d(k, stride, padding=(k-1)//2), models.py:91-94; a map with no output is refused here as torch refuses it
+            Hp, Wp = maxpool_out_size(x_in.H, k, stride), maxpool_out_size(x_in.W, k, stride)
             z = alloc_out(i, B, Hp, Wp, x_in.C)
             amax = new_ws(x_in.npix * x_in.C) if training else None
             pd = ew_desc(a=x_in, out=z, Bn=B, Hn=x_in.H, Wn=x_in.W, k=k)
