@@ -5,11 +5,46 @@
 // L1/L2), not MFMA work.  Weights are read directly from the fp32 master copy in tap-major order [k*k][C].
 // The forward optionally accumulates the per-channel sum / sum of squares for a following train-mode
 // BatchNorm into the same replicated fp64 buffers the MFMA conv epilogue uses.
+//
+// Layout of this file: the tile constants; the five kernels; ONE tile geometry (dw_tile_geometry) for both LDS-tiled
+// kernels; ONE route per op (dw_route_fwd / dw_route_dgrad / dw_route_wgrad) that maps a checked descriptor to a return code
+// or a kernel choice with its launch parameters; the extern "C" entries, each check -> route -> launch.
+// The order in which a route tests its refusals is observable (which code a doubly wrong descriptor gets) and is kept as it
+// was; so is what dyk_dwconv_wgrad_rows answers for an even k -- the row kernel's plane count, although dyk_dwconv_wgrad then
+// refuses the launch (no instantiation) -- see dw_route_wgrad.  tests/golden/dwconv_queries.json pins both.
+// Device helpers: dw_load_f32 (the fp32 weight-vector load of every kernel) and dw_clamp are shared.  The role view of GRAD, the
+// accumulate-and-store, the staging slot split, the `pre` activation, the BatchNorm vector load of the tiled data gradient and
+// the weight-gradient lane fold are written out in each kernel ON PURPOSE: as shared helpers each of them changed the
+// instructions of a kernel (order and register allocation, +0..30 instructions), and the probe cannot tell such a change from
+// its own run-to-run spread.  Written out, the ten tiled instantiations compile to the instructions of the version
+// before this layout, the other fifteen to the same instructions with a few of the prologue reordered.
 #include <type_traits>
 #include "dyk_common.h"
 
 namespace {
 
+// ---------------------------------------------------------------------------------------------- device helpers and tile constants
+// EPV (4 | 8) consecutive floats from a 16-byte aligned address (global or LDS) as float4 loads
+template <int EPV>
+__device__ inline void dw_load_f32(const float* p, float* out) {
+#pragma unroll
+    for (int j = 0; j < EPV; j += 4) {
+        const float4 q = *(const float4*)(p + j);
+        out[j] = q.x; out[j + 1] = q.y; out[j + 2] = q.z; out[j + 3] = q.w;
+    }
+}
+
+__device__ inline int dw_clamp(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+// ---- the LDS-tiled kernels' geometry.  Compile-time part: output tiles are TH x DW_TW pixels for CT <= 8 channel vectors, a
+// thread owns a strip of DW_XT pixels; the (TH + K - 1) x (DW_TW + K - 1) patch is staged with dw_patch_loads(K) 16-byte loads
+// per thread.  The kernels get CT and derive the rest with the functions dw_tile_geometry (host) uses.
+constexpr int DW_TW = 16, DW_XT = 4, DW_SPR = DW_TW / DW_XT;
+constexpr int dw_patch_loads(int k) { return k == 5 ? 8 : 6; }
+__host__ __device__ inline int dw_tile_rows(int CT) { return (256 / CT) / DW_SPR; }     // TH: thread = (vector, strip, row)
+__host__ __device__ inline int dw_slot_stride(int CT) { return CT | 1; }                // odd: <= 2-way bank conflicts
+
+// ---------------------------------------------------------------------------------------------- kernels
 // thread mapping: tx = channel vector in a group of CVB, ty = pixel lane; grid.x over channel-vector
 // groups, grid.y strides over output pixels
 template <typename T, bool GRAD>
@@ -24,12 +59,10 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DykDwDesc d, int CVB) {
     const T* __restrict__ x = GRAD ? (const T*)d.y : (const T*)d.x;     // tensor read
     T* __restrict__ y = GRAD ? (T*)d.x : (T*)d.y;                       // tensor written
     const int ld_src = GRAD ? d.ldy : d.ldx, ld_dst = GRAD ? d.ldx : d.ldy;
-    const int k = d.k, s = d.stride, pad = d.pad;
-    // forward: output grid (Ho, Wo), input (Hi, Wi).  GRAD: output grid is the *input* of the conv (Hi, Wi),
-    // source is the output gradient (Ho, Wo): dx[yi] += dy[(yi + pad - kh)/s] * w[kh] when divisible.
     const int Hout = GRAD ? d.Hi : d.Ho, Wout = GRAD ? d.Wi : d.Wo;
     const int Hsrc = GRAD ? d.Ho : d.Hi, Wsrc = GRAD ? d.Wo : d.Wi;
-    const long npix = (long)d.B * Hout * Wout;
+    const int k = d.k, s = d.stride, pad = d.pad;
+    // GRAD: dx[yi] += dy[(yi + pad - kh)/s] * w[kh] when divisible
     const bool accum = d.flags & DYK_EW_ACCUM;
     const bool stats = (!GRAD) && d.stats != nullptr;
     float s1[EPV], s2[EPV];
@@ -65,15 +98,9 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DykDwDesc d, int CVB) {
                         xs = xo * s + kw - pad;
                     }
                     if (xs < 0 || xs >= Wsrc) continue;
-                    float xv[EPV];
+                    float xv[EPV], wv[EPV];
                     vec_unpack<T>(*(const uint4*)(x + (((long)b * Hsrc + ys) * Wsrc + xs) * ld_src + c), xv);
-                    const float* wp = d.w + (long)(kh * k + kw) * d.C + c;
-                    const float4 w0 = *(const float4*)wp;
-                    float wv[8] = {w0.x, w0.y, w0.z, w0.w, 0.f, 0.f, 0.f, 0.f};
-                    if (EPV == 8) {
-                        const float4 w1 = *(const float4*)(wp + 4);
-                        wv[4] = w1.x; wv[5] = w1.y; wv[6] = w1.z; wv[7] = w1.w;
-                    }
+                    dw_load_f32<EPV>(d.w + (long)(kh * k + kw) * d.C + c, wv);
 #pragma unroll
                     for (int j = 0; j < EPV; ++j) acc[j] += xv[j] * wv[j];
                 }
@@ -94,6 +121,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DykDwDesc d, int CVB) {
         }
     }
     if (stats) {
+        // fold of the pixel lanes through LDS in lane order, then one fp64 atomic per (channel, sum) onto this workgroup row's replica
         float* mine = red + threadIdx.x * 16;
 #pragma unroll
         for (int j = 0; j < EPV; ++j) { mine[j] = s1[j]; mine[8 + j] = s2[j]; }
@@ -114,23 +142,23 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DykDwDesc d, int CVB) {
     }
 }
 
-// LDS-tiled stride-1 depthwise conv (bf16; forward, and the data gradient as the same correlation with the flipped kernel
+// LDS-tiled stride-1 depthwise conv (bf16 | fp16; forward, and the data gradient as the same correlation with the flipped kernel
 // and pad' = K - 1 - pad).  A workgroup stages the input patch of a TH x 16 pixel output tile for CT <= 8 channel vectors
 // in LDS -- every thread issues all of its (<= 8) 16-byte loads before anything waits, ONE memory round trip per tile
 // -- and the k x k taps are then ds_read_b128s.  (Its predecessor, a register-strip kernel that re-read the patch through
 // L1 in K dependent batches per strip, ran at 1.1-1.9 TB/s on the MobileNetV3 layers, latency-bound; it was removed once no
-// shape could reach it, see launch_dw_tile.)
+// shape could reach it, see dw_tile_geometry.)
 // Thread = (channel vector ct, strip of XT = 4 pixels, tile row); tile [rows][cols][S = CT|1] 16-byte slots (odd slot
 // stride: <= 2-way bank conflicts, irrelevant next to the VALU work); weights [K*K][CT*8] fp32 behind the tile.
 template <int K, bool GRAD, typename T = bf16_t>
 __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, int groups, unsigned m_ct, int tiles_x,
                                                           int tiles_y) {
     static_assert(sizeof(T) == 2, "16-bit elements (bf16 | f16)");
-    constexpr int EPV = 8, TW = 16, XT = 4, SPR = TW / XT, NS = XT + K - 1, IC = TW + K - 1;
-    constexpr int NLD = K == 5 ? 8 : 6;                       // staging loads per thread (host checks the tile fits)
+    constexpr int EPV = 8, TW = DW_TW, XT = DW_XT, SPR = DW_SPR, NS = XT + K - 1, IC = TW + K - 1;
+    constexpr int NLD = dw_patch_loads(K);                     // staging loads per thread (dw_tile_geometry checks the tile fits)
     extern __shared__ uint4 smem[];
-    const int S = CT | 1;
-    const int RT = (256 / CT) / SPR, TH = RT, IR = TH + K - 1;
+    const int S = dw_slot_stride(CT);
+    const int RT = dw_tile_rows(CT), TH = RT, IR = TH + K - 1;
     float* wl = (float*)(smem + IR * IC * S);
     int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int grp = bid % groups; bid /= groups;
@@ -142,14 +170,14 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, i
     const T* __restrict__ x = GRAD ? (const T*)d.y : (const T*)d.x;     // tensor read
     T* __restrict__ y = GRAD ? (T*)d.x : (T*)d.y;                       // tensor written
     const int ld_src = GRAD ? d.ldy : d.ldx, ld_dst = GRAD ? d.ldx : d.ldy;
-    const int padp = GRAD ? K - 1 - d.pad : d.pad;
     const int Hout = GRAD ? d.Hi : d.Ho, Wout = GRAD ? d.Wi : d.Wo;
     const int Hsrc = GRAD ? d.Ho : d.Hi, Wsrc = GRAD ? d.Wo : d.Wi;
+    const int padp = GRAD ? K - 1 - d.pad : d.pad;
     const int y0 = tyi * TH, x0 = txi * TW;
     const int tid = threadIdx.x;
     {   // ---- stage the patch: all loads first (clamped addresses), then the LDS stores (zeros outside the image)
         const int nvec = IR * IC * CT;
-        uint4 v[NLD];
+        uint4 u4[NLD];
         int dst[NLD], cts[NLD];
         unsigned okm = 0;
         const T* img = x + (long)b * Hsrc * Wsrc * ld_src + (long)cv0 * EPV;
@@ -161,9 +189,8 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, i
             const int row = (int)(q / IC), col = (int)(q - (unsigned)row * IC);
             const int ys = y0 + row - padp, xs = x0 + col - padp;
             const bool ok = idx < (unsigned)nvec && ys >= 0 && ys < Hsrc && xs >= 0 && xs < Wsrc && cv0 + ct < CV;
-            const int yc = ys < 0 ? 0 : (ys >= Hsrc ? Hsrc - 1 : ys), xc = xs < 0 ? 0 : (xs >= Wsrc ? Wsrc - 1 : xs);
             const int cc = cv0 + ct < CV ? ct : 0;
-            v[i] = *(const uint4*)(img + ((long)yc * Wsrc + xc) * ld_src + cc * EPV);
+            u4[i] = *(const uint4*)(img + ((long)dw_clamp(ys, Hsrc) * Wsrc + dw_clamp(xs, Wsrc)) * ld_src + cc * EPV);
             okm |= ok ? (1u << i) : 0u;
             cts[i] = cc;
             dst[i] = idx < (unsigned)nvec ? (row * IC + col) * S + ct : -1;
@@ -195,15 +222,13 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, i
                 constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
                 for (int i = 0; i < NLD; ++i) {
-                    float u[EPV];
-                    vec_unpack<T>(v[i], u);
-                    const float4 s0 = *(const float4*)(pl + cts[i] * 8), s1 = *(const float4*)(pl + cts[i] * 8 + 4);
-                    const float4 h0 = *(const float4*)(pl + CT * 8 + cts[i] * 8), h1 = *(const float4*)(pl + CT * 8 + cts[i] * 8 + 4);
-                    const float sc[EPV] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-                    const float sh[EPV] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+                    float u[EPV], sc[EPV], sh[EPV];
+                    vec_unpack<T>(u4[i], u);
+                    dw_load_f32<EPV>(pl + cts[i] * 8, sc);
+                    dw_load_f32<EPV>(pl + CT * 8 + cts[i] * 8, sh);
 #pragma unroll
                     for (int j = 0; j < EPV; ++j) u[j] = act_fwd_c<ACT>(u[j] * sc[j] + sh[j], d.pre_act);
-                    v[i] = vec_pack<T>(u);
+                    u4[i] = vec_pack<T>(u);
                 }
             };
             switch (d.pre_act) {
@@ -216,8 +241,8 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, i
         }
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            if (!((okm >> i) & 1u)) v[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (dst[i] >= 0) smem[dst[i]] = v[i];
+            if (!((okm >> i) & 1u)) u4[i] = make_uint4(0u, 0u, 0u, 0u);
+            if (dst[i] >= 0) smem[dst[i]] = u4[i];
         }
     }
     __syncthreads();
@@ -264,12 +289,7 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, i
         for (int kh = 0; kh < K; ++kh) {
             float wv[K][EPV];
 #pragma unroll
-            for (int kw = 0; kw < K; ++kw) {
-                const float4 w0 = *(const float4*)(wl + ((kh * K + kw) * CT + ct) * 8);
-                const float4 w1 = *(const float4*)(wl + ((kh * K + kw) * CT + ct) * 8 + 4);
-                wv[kw][0] = w0.x; wv[kw][1] = w0.y; wv[kw][2] = w0.z; wv[kw][3] = w0.w;
-                wv[kw][4] = w1.x; wv[kw][5] = w1.y; wv[kw][6] = w1.z; wv[kw][7] = w1.w;
-            }
+            for (int kw = 0; kw < K; ++kw) dw_load_f32<EPV>(wl + ((kh * K + kw) * CT + ct) * 8, wv[kw]);
             const uint4* prow = smem + ((r + kh) * IC + strip * XT) * S + ct;
 #pragma unroll
             for (int q = 0; q < NS; ++q) {
@@ -349,80 +369,43 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(DykDwDesc d, int CT, i
     }
 }
 
-// Every stride-1 k = 3 | 5 16-bit problem runs here.  CT is 1..8 by construction, and the patch of every CT fits the NLD * 256
-// staging loads (IR * IC * CT vectors; RT = (256 / CT) / 4, IR = RT + K - 1, IC = 16 + K - 1):
-//   CT          1     2     3     4     5     6     7     8
-//   k = 3    1188  1224  1242  1296  1260  1296  1386  1440   of 1536
-//   k = 5    1360  1440  1500  1600  1600  1680  1820  1920   of 2048
-// and LDS stays below 64 KB (k = 3: 29.4 KB at most, k = 5: 40.5 KB).  What is left to refuse is a grid of 2^31 workgroups.
-template <int K, bool GRAD, typename T = bf16_t>
-int launch_dw_tile(const DykDwDesc* d, hipStream_t stream) {
-    constexpr int TW = 16, IC = TW + K - 1, NLD = K == 5 ? 8 : 6;
-    const int CV = d->C / 8;
-    const int groups = (CV + 7) / 8, CT = (CV + groups - 1) / groups;
-    const int RT = (256 / CT) / 4, IR = RT + K - 1, S = CT | 1;
-    if (IR * IC * CT > NLD * 256) return DYK_ERR_UNSUPPORTED;
-    const int Hout = GRAD ? d->Hi : d->Ho, Wout = GRAD ? d->Wi : d->Wo;
-    const int tiles_x = (Wout + TW - 1) / TW, tiles_y = (Hout + RT - 1) / RT;
-    size_t lds = (size_t)IR * IC * S * 16 + (size_t)K * K * CT * 8 * 4 + (size_t)CT * 16 * 4;   // patch | weights | pre scale, shift
-    if (lds < 256 * 16 * 4 + 2048) lds = 256 * 16 * 4 + 2048;            // the statistics reduction reuses the patch
-    const unsigned m_ct = (unsigned)(0xFFFFFFFFu / (unsigned)CT) + 1u;   // idx / CT == umulhi(idx, m_ct) for idx < 2^32 / CT
-    const long nblk = (long)groups * tiles_x * tiles_y * d->B;
-    if (nblk >= (1L << 31) || lds > 64 * 1024) return DYK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((dwconv_tile_kernel<K, GRAD, T>), dim3((unsigned)nblk), dim3(256), lds, stream, *d, CT, groups,
-                       m_ct, tiles_x, tiles_y);
-    return DYK_OK;
-}
-
-// Stride-2 fast path (MobileNet down-sampling layers): K and the stride are compile-time, so the taps of a pixel are a
+// Stride-2 data gradient (MobileNet down-sampling layers): K and the stride are compile-time, so the taps of a pixel are a
 // fixed, unrolled set whose loads are issued together -- clamped coordinates, values zeroed afterwards (dwconv_kernel
 // walks runtime loops with a branch around every load: one memory round trip per tap).
-//   forward : y[yo, xo] = sum_{kh,kw} x[2 yo + kh - pad, 2 xo + kw - pad] w[kh, kw]              (K*K loads)
-//   gradient: dx[yi, xi] = sum over the taps of yi's / xi's parity, kh = (yi + pad) % 2 + 2 a:
-//             dy[(yi + pad - kh) / 2, (xi + pad - kw) / 2] w[kh, kw]                              (ceil(K/2)^2 loads)
-template <typename T, int K, bool GRAD>
-__global__ __launch_bounds__(256) void dwconv_s2_kernel(DykDwDesc d, int CVB) {
+//   dx[yi, xi] = sum over the taps of yi's / xi's parity, kh = (yi + pad) % 2 + 2 a:
+//                dy[(yi + pad - kh) / 2, (xi + pad - kw) / 2] w[kh, kw]                              (ceil(K/2)^2 loads)
+// (The stride-2 FORWARD runs on dwconv_kernel, which measured faster than the forward form this kernel once had.)
+template <int K, typename T>
+__global__ __launch_bounds__(256) void dwconv_s2_dgrad_kernel(DykDwDesc d, int CVB) {
     constexpr int EPV = ElemTraits<T>::EPV;
-    constexpr int KT = GRAD ? (K + 1) / 2 : K;                 // taps per dimension a pixel touches
-    __shared__ float red[256 * 2 * 8];
+    constexpr int KT = (K + 1) / 2;                            // taps per dimension a pixel touches
     const int PY = 256 / CVB;
     const int tx = threadIdx.x % CVB, ty = threadIdx.x / CVB;
-    const int cv = blockIdx.x * CVB + tx;
-    const int c = cv * EPV;
-    const bool active = c < d.C;
-    const T* __restrict__ x = GRAD ? (const T*)d.y : (const T*)d.x;     // tensor read
-    T* __restrict__ y = GRAD ? (T*)d.x : (T*)d.y;                       // tensor written
-    const int ld_src = GRAD ? d.ldy : d.ldx, ld_dst = GRAD ? d.ldx : d.ldy;
+    const int c = (blockIdx.x * CVB + tx) * EPV;
+    const T* __restrict__ dy = (const T*)d.y;                  // read: output gradient [B, Ho, Wo, C]
+    T* __restrict__ dx = (T*)d.x;                              // written: input gradient [B, Hi, Wi, C]
     const int pad = d.pad;
-    const int Hout = GRAD ? d.Hi : d.Ho, Wout = GRAD ? d.Wi : d.Wo;
-    const int Hsrc = GRAD ? d.Ho : d.Hi, Wsrc = GRAD ? d.Wo : d.Wi;
     const bool accum = d.flags & DYK_EW_ACCUM;
-    const bool stats = (!GRAD) && d.stats != nullptr;
-    float s1[EPV], s2[EPV];
-#pragma unroll
-    for (int j = 0; j < EPV; ++j) s1[j] = s2[j] = 0.f;
-    if (active) {
-        const int nrows = d.B * Hout;
+    if (c < d.C) {
+        const int nrows = d.B * d.Hi;
         for (int row = blockIdx.y; row < nrows; row += gridDim.y) {
-            const int b = row / Hout, yo = row - b * Hout;
-            const int kh0 = GRAD ? (yo + pad) & 1 : 0;
-            for (int xo = ty; xo < Wout; xo += PY) {
-                const int kw0 = GRAD ? (xo + pad) & 1 : 0;
+            const int b = row / d.Hi, yi = row - b * d.Hi;
+            const int kh0 = (yi + pad) & 1;
+            for (int xi = ty; xi < d.Wi; xi += PY) {
+                const int kw0 = (xi + pad) & 1;
                 uint4 raw[KT][KT];
                 bool ok[KT][KT];
 #pragma unroll
                 for (int a = 0; a < KT; ++a) {
-                    const int kh = GRAD ? kh0 + 2 * a : a;
-                    const int ys = GRAD ? (yo + pad - kh) >> 1 : yo * 2 + kh - pad;
-                    const bool yok = kh < K && ys >= 0 && ys < Hsrc && (!GRAD || yo + pad - kh >= 0);
-                    const int yc = ys < 0 ? 0 : (ys >= Hsrc ? Hsrc - 1 : ys);
+                    const int kh = kh0 + 2 * a;
+                    const int yo = (yi + pad - kh) >> 1;
+                    const bool yok = kh < K && yo >= 0 && yo < d.Ho && yi + pad - kh >= 0;
 #pragma unroll
                     for (int e = 0; e < KT; ++e) {
-                        const int kw = GRAD ? kw0 + 2 * e : e;
-                        const int xs = GRAD ? (xo + pad - kw) >> 1 : xo * 2 + kw - pad;
-                        ok[a][e] = yok && kw < K && xs >= 0 && xs < Wsrc && (!GRAD || xo + pad - kw >= 0);
-                        const int xc = xs < 0 ? 0 : (xs >= Wsrc ? Wsrc - 1 : xs);
-                        raw[a][e] = *(const uint4*)(x + (((long)b * Hsrc + yc) * Wsrc + xc) * ld_src + c);
+                        const int kw = kw0 + 2 * e;
+                        const int xo = (xi + pad - kw) >> 1;
+                        ok[a][e] = yok && kw < K && xo >= 0 && xo < d.Wo && xi + pad - kw >= 0;
+                        raw[a][e] = *(const uint4*)(dy + (((long)b * d.Ho + dw_clamp(yo, d.Ho)) * d.Wo + dw_clamp(xo, d.Wo)) * d.ldy + c);
                     }
                 }
                 float acc[EPV];
@@ -432,52 +415,23 @@ __global__ __launch_bounds__(256) void dwconv_s2_kernel(DykDwDesc d, int CVB) {
                 for (int a = 0; a < KT; ++a)
 #pragma unroll
                     for (int e = 0; e < KT; ++e) {
-                        const int kh = GRAD ? kh0 + 2 * a : a, kw = GRAD ? kw0 + 2 * e : e;
+                        const int kh = kh0 + 2 * a, kw = kw0 + 2 * e;
                         const int t = (kh < K && kw < K) ? kh * K + kw : 0;
-                        const float* wp = d.w + (long)t * d.C + c;
-                        const float4 w0 = *(const float4*)wp;
-                        float wv[8] = {w0.x, w0.y, w0.z, w0.w, 0.f, 0.f, 0.f, 0.f};
-                        if (EPV == 8) {
-                            const float4 w1 = *(const float4*)(wp + 4);
-                            wv[4] = w1.x; wv[5] = w1.y; wv[6] = w1.z; wv[7] = w1.w;
-                        }
-                        float xv[EPV];
+                        float xv[EPV], wv[EPV];
+                        dw_load_f32<EPV>(d.w + (long)t * d.C + c, wv);
                         vec_unpack<T>(raw[a][e], xv);
                         const bool in = ok[a][e];
 #pragma unroll
                         for (int j = 0; j < EPV; ++j) acc[j] += in ? xv[j] * wv[j] : 0.f;
                     }
-                if (stats) {
-#pragma unroll
-                    for (int j = 0; j < EPV; ++j) { s1[j] += acc[j]; s2[j] += acc[j] * acc[j]; }
-                }
-                T* yp = y + ((long)row * Wout + xo) * ld_dst + c;
+                T* xp = dx + ((long)row * d.Wi + xi) * d.ldx + c;
                 if (accum) {
                     float old[EPV];
-                    vec_unpack<T>(*(const uint4*)yp, old);
+                    vec_unpack<T>(*(const uint4*)xp, old);
 #pragma unroll
                     for (int j = 0; j < EPV; ++j) acc[j] += old[j];
                 }
-                *(uint4*)yp = vec_pack<T>(acc);
-            }
-        }
-    }
-    if (stats) {
-        float* mine = red + threadIdx.x * 16;
-#pragma unroll
-        for (int j = 0; j < EPV; ++j) { mine[j] = s1[j]; mine[8 + j] = s2[j]; }
-        __syncthreads();
-        if (ty == 0 && active) {
-            for (int q = 1; q < PY; ++q) {
-                const float* o = red + (q * CVB + tx) * 16;
-#pragma unroll
-                for (int j = 0; j < EPV; ++j) { s1[j] += o[j]; s2[j] += o[8 + j]; }
-            }
-            double* st = d.stats + (size_t)(blockIdx.y % (unsigned)(d.stats_slots > 0 ? d.stats_slots : 1)) * 2 * d.C;
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) {
-                atomicAdd(st + c + j, (double)s1[j]);
-                atomicAdd(st + d.C + c + j, (double)s2[j]);
+                *(uint4*)xp = vec_pack<T>(acc);
             }
         }
     }
@@ -498,7 +452,6 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(DykDwDesc d, int CVB)
     const int kh = blockIdx.z;
     const T* __restrict__ x = (const T*)d.x;
     const T* __restrict__ dy = (const T*)d.y;       // output gradient [B,Ho,Wo,C]
-    const long npix = (long)d.B * d.Ho * d.Wo;
     float acc[K][EPV];
 #pragma unroll
     for (int t = 0; t < K; ++t)
@@ -513,8 +466,6 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(DykDwDesc d, int CVB)
 #pragma unroll
         for (int j = 0; j < EPV; ++j) { psc[j] = d.pre[c + j]; psh[j] = d.pre[d.C + c + j]; }
     }
-    // branch-free for the activations the depthwise blocks use (ReLU, ReLU6, h-swish, leaky, linear):
-    //   act(t) = clamp(t, lo, hi) * (mulx ? clamp(t + 3, 0, 6) / 6 : 1)   with leaky as max(t, 0.1 t)
     const int pact = d.pre_act;
     const bool p_generic = pre && !(pact == DYK_ACT_LINEAR || pact == DYK_ACT_RELU || pact == DYK_ACT_RELU6 || pact == DYK_ACT_HSWISH ||
                                     pact == DYK_ACT_LEAKY);
@@ -556,11 +507,8 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(DykDwDesc d, int CVB)
                         graw[o] = *(const uint4*)(dy + ((long)row * d.Wo + xo) * d.ldy + c);
                     }
 #pragma unroll
-                    for (int sl = 0; sl < XT + K - 1; ++sl) {
-                        const int xi = xo0 - d.pad + sl;
-                        const int xc = xi < 0 ? 0 : (xi >= d.Wi ? d.Wi - 1 : xi);
-                        xraw[sl] = *(const uint4*)(xrow + (long)xc * d.ldx);
-                    }
+                    for (int sl = 0; sl < XT + K - 1; ++sl)
+                        xraw[sl] = *(const uint4*)(xrow + (long)dw_clamp(xo0 - d.pad + sl, d.Wi) * d.ldx);
 #pragma unroll
                     for (int o = 0; o < XT; ++o) {
                         vec_unpack<T>(graw[o], g[o]);
@@ -595,10 +543,7 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(DykDwDesc d, int CVB)
             const int xi0 = xo * d.stride - d.pad;
             uint4 xraw[K];
 #pragma unroll
-            for (int t = 0; t < K; ++t) {
-                const int xi = xi0 + t;
-                xraw[t] = *(const uint4*)(xrow + (long)(xi < 0 ? 0 : (xi >= d.Wi ? d.Wi - 1 : xi)) * d.ldx);
-            }
+            for (int t = 0; t < K; ++t) xraw[t] = *(const uint4*)(xrow + (long)dw_clamp(xi0 + t, d.Wi) * d.ldx);
 #pragma unroll
             for (int t = 0; t < K; ++t) {
                 const int xi = xi0 + t;
@@ -656,11 +601,11 @@ template <int K, bool PRE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void dwconv_wgrad_tile_kernel(DykDwDesc d, int CT, int groups, unsigned m_ct, int tiles_x,
                                                                 int tiles_y, int P) {
     using T = bf16_t;
-    constexpr int EPV = 8, TW = 16, XT = 4, SPR = TW / XT, NS = XT + K - 1, IC = TW + K - 1;
-    constexpr int NLX = K == 5 ? 8 : 6, NLG = 4, NLD = NLX + NLG;
+    constexpr int EPV = 8, TW = DW_TW, XT = DW_XT, SPR = DW_SPR, NS = XT + K - 1, IC = TW + K - 1;
+    constexpr int NLX = dw_patch_loads(K), NLG = 4, NLD = NLX + NLG;     // loads per thread: x patch, dy tile (TH * TW * CT <= 4 * 256)
     extern __shared__ uint4 smem[];
-    const int S = CT | 1;
-    const int TH = (256 / CT) / SPR, IR = TH + K - 1;
+    const int S = dw_slot_stride(CT);
+    const int TH = dw_tile_rows(CT), IR = TH + K - 1;
     uint4* patch = smem;                                       // [IR][IC][S]  x
     uint4* gtile = smem + IR * IC * S;                         // [TH][TW][S]  dy
     const int tid = threadIdx.x;
@@ -698,8 +643,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (i < NLX) {
                 const int ys = y0 + row - d.pad, xs = x0 + col - d.pad;
                 const bool ok = role[i] >= 0 && ys >= 0 && ys < d.Hi && xs >= 0 && xs < d.Wi;
-                const int yc = ys < 0 ? 0 : (ys >= d.Hi ? d.Hi - 1 : ys), xc = xs < 0 ? 0 : (xs >= d.Wi ? d.Wi - 1 : xs);
-                v[i] = *(const uint4*)(ximg + ((long)yc * d.Wi + xc) * d.ldx + ct * EPV);
+                v[i] = *(const uint4*)(ximg + ((long)dw_clamp(ys, d.Hi) * d.Wi + dw_clamp(xs, d.Wi)) * d.ldx + ct * EPV);
                 okm |= ok ? (1u << i) : 0u;
             } else {
                 const int ys = y0 + row, xs = x0 + col;
@@ -724,6 +668,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // DykDwDesc.pre (PRE): x holds the RAW output of the producing conv; z = dtype(act(scale * u + shift)) is formed between the
     // loads and the LDS stores -- the patch then holds exactly what the separate normalise pass would have stored.  Branch-free
     // for ReLU / ReLU6 / h-swish / leaky / linear: act(t) = clamp(max(t, leak * t), lo, hi), h-swish t * clamp(t + 3, 0, 6) / 6
+    // (the same expressions as in dwconv_wgrad_kernel: DESIGN 5.4 relies on both giving the same bf16 values)
     float* pl = (float*)(smem + (IR * IC + TH * TW) * S);      // [2][CT * 8] scale | shift of this channel group
     const int pact = d.pre_act;
     const bool p_generic = !(pact == DYK_ACT_LINEAR || pact == DYK_ACT_RELU || pact == DYK_ACT_RELU6 || pact == DYK_ACT_HSWISH ||
@@ -808,7 +753,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
     }
-    // ---- fold the pixel lanes through LDS in lane order, one tap at a time
+    // ---- fold the pixel lanes through LDS in lane order, one tap at a time; plane = this workgroup of its channel group.
+    // (the fold of dwconv_wgrad_kernel with lane stride K * CT and a float4 store; written out in both, see the note on helpers
+    // at the top of the file)
     __syncthreads();
     float* red = (float*)smem;
 #pragma unroll
@@ -845,43 +792,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-struct DwWgTile { int CT, groups, tiles_x, tiles_y, P; unsigned m_ct; size_t lds; };
-inline int dw_wgrad_tile_target() {
-    return 512;                                                // workgroups per launch (two resident per CU)
+// ---------------------------------------------------------------------------------------------- host: geometry and routes
+// geometry of the LDS-tiled kernels for C channels, kernel size k (3 | 5) and B output maps of Hout x Wout.  CT is 1..8 by
+// construction, and the patch of every CT fits the staging loads (nvec of nld):
+//   CT          1     2     3     4     5     6     7     8
+//   k = 3    1188  1224  1242  1296  1260  1296  1386  1440   of 1536
+//   k = 5    1360  1440  1500  1600  1600  1680  1820  1920   of 2048
+struct DwGeom {
+    int CT, groups, S, TH, IR, IC, tiles_x, tiles_y;
+    int nvec, nld;              // patch vectors, and the staging limit they must fit: dw_patch_loads(k) * 256
+    unsigned m_ct;              // idx / CT == umulhi(idx, m_ct) for idx < 2^32 / CT
+    long ntiles;                // B * tiles_y * tiles_x
+    bool fits() const { return nvec <= nld; }
+};
+inline DwGeom dw_tile_geometry(int C, int k, int Hout, int Wout, int B) {
+    DwGeom g;
+    const int CV = C / 8;
+    g.groups = (CV + 7) / 8;
+    g.CT = (CV + g.groups - 1) / g.groups;
+    g.S = dw_slot_stride(g.CT);
+    g.TH = dw_tile_rows(g.CT);
+    g.IR = g.TH + k - 1;
+    g.IC = DW_TW + k - 1;
+    g.tiles_x = (Wout + DW_TW - 1) / DW_TW;
+    g.tiles_y = (Hout + g.TH - 1) / g.TH;
+    g.nvec = g.IR * g.IC * g.CT;
+    g.nld = dw_patch_loads(k) * 256;
+    g.m_ct = (unsigned)(0xFFFFFFFFu / (unsigned)g.CT) + 1u;
+    g.ntiles = (long)B * g.tiles_x * g.tiles_y;
+    return g;
 }
-// geometry of the tiled weight gradient for this problem; false = not eligible (the row kernel runs)
-inline bool dw_wgrad_tile_cfg(const DykDwDesc* d, DwWgTile* c) {
-    const int K = d->k;
-    if (d->dtype != DYK_BF16 || d->stride != 1 || (K != 3 && K != 5) || dw_wgrad_tile_target() <= 0) return false;
-    const int CV = d->C / 8, NLX = K == 5 ? 8 : 6;
-    c->groups = (CV + 7) / 8;
-    c->CT = (CV + c->groups - 1) / c->groups;
-    const int TH = (256 / c->CT) / 4, IR = TH + K - 1, IC = 16 + K - 1, S = c->CT | 1;
-    if (IR * IC * c->CT > NLX * 256 || (256 / c->CT) / K < 1 || IR > 255) return false;
-    c->tiles_x = (d->Wo + 15) / 16;
-    c->tiles_y = (d->Ho + TH - 1) / TH;
-    const long ntiles = (long)d->B * c->tiles_x * c->tiles_y;
-    if (ntiles >= (1L << 30)) return false;
-    // (two workgroups per CU; three for the 3x3 kernel at 164 VGPRs measured equal: 70 / 87 / 20 / 29 us against 65 / 88 / 20 / 29)
-    long p0 = dw_wgrad_tile_target() / c->groups;
-    if (p0 < 1) p0 = 1;
-    if (p0 > ntiles) p0 = ntiles;
-    const long rounds = (ntiles + p0 - 1) / p0;
-    c->P = (int)((ntiles + rounds - 1) / rounds);
-    c->m_ct = (unsigned)(0xFFFFFFFFu / (unsigned)c->CT) + 1u;
-    c->lds = (size_t)(IR * IC + TH * 16) * S * 16 + (size_t)2 * c->CT * 8 * 4;             // patch | dy tile | pre scale, shift
-    if (c->lds < 256 * 8 * 4) c->lds = 256 * 8 * 4;
-    return c->lds <= 64 * 1024;
-}
-inline int launch_dw_wgrad_tile(const DykDwDesc* d, const DwWgTile& c, hipStream_t s) {
-    const dim3 grid((unsigned)(c.groups * c.P));
-#define DYK_DWW(KK, PP) hipLaunchKernelGGL((dwconv_wgrad_tile_kernel<KK, PP>), grid, dim3(256), c.lds, s, *d, c.CT, c.groups, c.m_ct, c.tiles_x, c.tiles_y, c.P)
-    if (d->k == 3) { if (d->pre) DYK_DWW(3, true); else DYK_DWW(3, false); }
-    else { if (d->pre) DYK_DWW(5, true); else DYK_DWW(5, false); }
-#undef DYK_DWW
-    DYK_LAUNCH_CHECK();
-    return DYK_OK;
-}
+
+// What an entry point does with a checked descriptor: a return code, or the kernel with its launch parameters.  The kernels take
+// (d, CVB) on a dw_route_rows grid, or, tiled, (d, CT, groups, m_ct, tiles_x, tiles_y [, P]) on the tile geometry
+struct DwRoute {
+    int rc;
+    const void* kernel;         // null: no instantiation for this k (dw_route_wgrad)
+    bool tiled;
+    dim3 grid;
+    size_t lds;
+    DwGeom g;                   // tiled
+    int CVB;                    // rows
+    int planes;                 // weight gradient: workgroup rows (rows) | workgroups per channel group P (tiled)
+};
+inline DwRoute dw_refuse(int rc) { DwRoute r = {}; r.rc = rc; return r; }
+// the K in {3, 5} instantiation of a kernel template whose first parameter is K
+#define DW_K35(k, KERNEL, ...) ((k) == 3 ? (const void*)KERNEL<3, __VA_ARGS__> : (const void*)KERNEL<5, __VA_ARGS__>)
 
 int check_dw(const DykDwDesc* d) {
     if (!d || !d->x || !d->y || d->B <= 0 || d->C <= 0 || d->k <= 0 || d->k > 7 || d->stride <= 0) return DYK_ERR_ARG;
@@ -892,136 +848,154 @@ int check_dw(const DykDwDesc* d) {
     return DYK_OK;
 }
 
-// grid.x = channel-vector groups, grid.y = image rows (strided), capped at cap_blocks workgroups
-inline int grid2d(int CV, long nrows, int* gx, int* gy, int cap_blocks) {
-    int CVB = 1;
-    while (CVB < CV && CVB < 32) CVB <<= 1;
-    *gx = (CV + CVB - 1) / CVB;
+// a (d, CVB) kernel: grid.x = channel-vector groups, grid.y = image rows (strided), capped at cap_blocks workgroups
+inline DwRoute dw_route_rows(const DykDwDesc* d, const void* fn, long nrows, int cap_blocks, int gz = 1) {
+    DwRoute r = {};
+    r.kernel = fn;
+    const int CV = d->C / (d->dtype == DYK_F32 ? 4 : 8);
+    r.CVB = 1;
+    while (r.CVB < CV && r.CVB < 32) r.CVB <<= 1;
+    const int gx = (CV + r.CVB - 1) / r.CVB;
     long g = nrows;
-    const long cap = cap_blocks / *gx > 0 ? cap_blocks / *gx : 1;
+    const long cap = cap_blocks / gx > 0 ? cap_blocks / gx : 1;
     if (g > cap) g = cap;
     if (g < 1) g = 1;
-    *gy = (int)g;
-    return CVB;
+    r.grid = dim3(gx, (unsigned)g, gz);
+    r.planes = (int)g;
+    return r;
+}
+
+// the shapes of the LDS-tiled kernels; the forward takes them in both 16-bit types (dyk_dwconv_tile_ok), the gradients in bf16
+inline bool dw_k35_s1(const DykDwDesc* d) { return d->stride == 1 && (d->k == 3 || d->k == 5); }
+inline bool dw_fwd_tiled_domain(const DykDwDesc* d) { return dw_k35_s1(d) && (d->dtype == DYK_BF16 || d->dtype == DYK_F16); }
+
+// the LDS-tiled forward / data gradient.  Every problem of its domain runs: the patch always fits (table above) and LDS stays
+// below 64 KB (k = 3: 29.4 KB at most, k = 5: 40.5 KB); what is left to refuse is a grid of 2^31 workgroups
+inline DwRoute dw_route_tiled(const DykDwDesc* d, bool grad) {
+    DwRoute r = {};
+    const DwGeom& g = r.g = dw_tile_geometry(d->C, d->k, grad ? d->Hi : d->Ho, grad ? d->Wi : d->Wo, d->B);
+    if (!g.fits()) return dw_refuse(DYK_ERR_UNSUPPORTED);
+    r.lds = (size_t)g.IR * g.IC * g.S * 16 + (size_t)d->k * d->k * g.CT * 8 * 4 + (size_t)g.CT * 16 * 4;   // patch | weights | pre scale, shift
+    if (r.lds < 256 * 16 * 4 + 2048) r.lds = 256 * 16 * 4 + 2048;            // the statistics reduction reuses the patch
+    if (g.groups * g.ntiles >= (1L << 31) || r.lds > 64 * 1024) return dw_refuse(DYK_ERR_UNSUPPORTED);
+    r.tiled = true;
+    r.kernel = grad                 ? DW_K35(d->k, dwconv_tile_kernel, true, bf16_t)
+             : d->dtype == DYK_F16 ? DW_K35(d->k, dwconv_tile_kernel, false, f16_t)
+                                   : DW_K35(d->k, dwconv_tile_kernel, false, bf16_t);
+    r.grid = dim3((unsigned)(g.groups * g.ntiles));
+    return r;
+}
+
+DwRoute dw_route_fwd(const DykDwDesc* d) {
+    if (!d->w) return dw_refuse(DYK_ERR_ARG);
+    // fp16 is the inference type: the same kernel choice as bf16, no BatchNorm statistics, no normalise-on-load (train-mode forms)
+    if (d->dtype == DYK_F16 && (d->stats || d->pre)) return dw_refuse(DYK_ERR_UNSUPPORTED);
+    if (dw_fwd_tiled_domain(d)) return dw_route_tiled(d, false);
+    if (d->pre) return dw_refuse(DYK_ERR_UNSUPPORTED);       // normalise + activation on load: the LDS-tiled kernel only
+    // (stride 2 too: the generic kernel measured faster than a forward with compile-time taps)
+    return dw_route_rows(d, d->dtype == DYK_BF16  ? (const void*)dwconv_kernel<bf16_t, false>
+                            : d->dtype == DYK_F16 ? (const void*)dwconv_kernel<f16_t, false>
+                                                  : (const void*)dwconv_kernel<float, false>,
+                         (long)d->B * d->Ho, 4096);
+}
+
+DwRoute dw_route_dgrad(const DykDwDesc* d) {
+    if (d->dtype == DYK_F16) return dw_refuse(DYK_ERR_UNSUPPORTED);
+    if (!d->w) return dw_refuse(DYK_ERR_ARG);
+    const bool k35 = (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16;
+    if (d->res) {                    // fused BatchNorm-backward reduce: LDS-tiled kernel only, no accumulate form
+        if (!d->bn || !d->stats || d->stats_slots <= 0 || d->ldr < d->C || d->ldr % 8 || ((uintptr_t)d->res % 16)) return dw_refuse(DYK_ERR_ARG);
+        if (!(k35 && d->stride == 1) || (d->flags & DYK_EW_ACCUM)) return dw_refuse(DYK_ERR_UNSUPPORTED);
+    }
+    if (k35 && d->stride == 1) return dw_route_tiled(d, true);
+    return dw_route_rows(d, k35 && d->stride == 2   ? DW_K35(d->k, dwconv_s2_dgrad_kernel, bf16_t)
+                            : d->dtype == DYK_BF16 ? (const void*)dwconv_kernel<bf16_t, true>
+                                                   : (const void*)dwconv_kernel<float, true>,
+                         (long)d->B * d->Hi, 4096);
+}
+
+template <typename T>
+const void* dw_wgrad_rows_kernel(int k) {
+    switch (k) {
+    case 1: return (const void*)dwconv_wgrad_kernel<T, 1>;
+    case 3: return (const void*)dwconv_wgrad_kernel<T, 3>;
+    case 5: return (const void*)dwconv_wgrad_kernel<T, 5>;
+    case 7: return (const void*)dwconv_wgrad_kernel<T, 7>;
+    default: return nullptr;
+    }
+}
+
+// The persistent tiled kernel where it is eligible (bf16, stride 1, k = 3 | 5), else the row kernel.  The weight gradient adds to
+// the shared geometry only what is its own: the dy tile and its LDS layout, IR <= 255 (the staging roles pack a row into 8 bits),
+// at least one pixel lane per kernel row, ntiles < 2^30, and P.  An even k gets the row kernel's grid and plane count but no
+// kernel: dyk_dwconv_wgrad_rows answers the planes, dyk_dwconv_wgrad refuses the launch (as recorded in dwconv_queries.json)
+DwRoute dw_route_wgrad(const DykDwDesc* d) {
+    if (d->dtype == DYK_F16) return dw_refuse(DYK_ERR_UNSUPPORTED);
+    if (d->dtype == DYK_BF16 && dw_k35_s1(d)) {
+        DwRoute r = {};
+        const DwGeom& g = r.g = dw_tile_geometry(d->C, d->k, d->Ho, d->Wo, d->B);
+        r.lds = (size_t)(g.IR * g.IC + g.TH * DW_TW) * g.S * 16 + (size_t)2 * g.CT * 8 * 4;      // patch | dy tile | pre scale, shift
+        if (r.lds < 256 * 8 * 4) r.lds = 256 * 8 * 4;                                            // the lane fold reuses the patch
+        if (g.fits() && (256 / g.CT) / d->k >= 1 && g.IR <= 255 && g.ntiles < (1L << 30) && r.lds <= 64 * 1024) {
+            // 512 workgroups per launch, two resident per CU (three for the 3x3 kernel at 164 VGPRs measured equal: 70 / 87 /
+            // 20 / 29 us against 65 / 88 / 20 / 29), the tiles dealt evenly over the rounds
+            long p0 = 512 / g.groups;
+            if (p0 < 1) p0 = 1;
+            if (p0 > g.ntiles) p0 = g.ntiles;
+            const long rounds = (g.ntiles + p0 - 1) / p0;
+            r.planes = (int)((g.ntiles + rounds - 1) / rounds);
+            r.tiled = true;
+            r.kernel = d->pre ? DW_K35(d->k, dwconv_wgrad_tile_kernel, true) : DW_K35(d->k, dwconv_wgrad_tile_kernel, false);
+            r.grid = dim3((unsigned)(g.groups * r.planes));
+            return r;
+        }
+    }
+    // few, long-running workgroups: every workgroup ends with one atomic per (tap, channel) on only k*k*C addresses
+    return dw_route_rows(d, d->dtype == DYK_BF16 ? dw_wgrad_rows_kernel<bf16_t>(d->k) : dw_wgrad_rows_kernel<float>(d->k), (long)d->B * d->Ho,
+                         768 / d->k, d->k);
+}
+
+int dw_launch(const DykDwDesc* d, const DwRoute& r, hipStream_t s) {
+    if (r.rc != DYK_OK) return r.rc;
+    if (!r.kernel) return DYK_ERR_UNSUPPORTED;
+    DykDwDesc desc = *d;
+    DwGeom g = r.g;
+    int CVB = r.CVB, P = r.planes;
+    void* rows_args[] = {&desc, &CVB};
+    void* tile_args[] = {&desc, &g.CT, &g.groups, &g.m_ct, &g.tiles_x, &g.tiles_y, &P};    // P: the weight gradient only
+    if (hipLaunchKernel(r.kernel, r.grid, dim3(256), r.tiled ? tile_args : rows_args, r.lds, s) != hipSuccess) return DYK_ERR_HIP;
+    DYK_LAUNCH_CHECK();
+    return DYK_OK;
 }
 
 }  // namespace
 
 extern "C" int dyk_dwconv_fwd(const DykDwDesc* d, void* stream) {
     const int rc = check_dw(d);
-    if (rc) return rc;
-    if (!d->w) return DYK_ERR_ARG;
-    const int epv = d->dtype == DYK_F32 ? 4 : 8;
-    int gx, gy;
-    const int CVB = grid2d(d->C / epv, (long)d->B * d->Ho, &gx, &gy, 4096);
-    if (d->dtype == DYK_F16) {
-        // the inference type: the same kernel choice as bf16, no BatchNorm statistics, no normalise-on-load (train-mode forms)
-        if (d->stats || d->pre) return DYK_ERR_UNSUPPORTED;
-        if (d->stride == 1 && (d->k == 3 || d->k == 5)) {
-            const int rt = d->k == 3 ? launch_dw_tile<3, false, f16_t>(d, (hipStream_t)stream) : launch_dw_tile<5, false, f16_t>(d, (hipStream_t)stream);
-            if (rt == DYK_OK) DYK_LAUNCH_CHECK();
-            return rt;
-        }
-        hipLaunchKernelGGL((dwconv_kernel<f16_t, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-        DYK_LAUNCH_CHECK();
-        return DYK_OK;
-    }
-    if (d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16) {
-        const int rt = d->k == 3 ? launch_dw_tile<3, false>(d, (hipStream_t)stream) : launch_dw_tile<5, false>(d, (hipStream_t)stream);
-        if (rt == DYK_OK) DYK_LAUNCH_CHECK();
-        return rt;
-    }
-    if (d->pre) return DYK_ERR_UNSUPPORTED;        // normalise + activation on load: the LDS-tiled kernel only (dyk_dwconv_tile_ok)
-    if (d->dtype == DYK_BF16)      // (stride 2 forward: the generic kernel measured faster than dwconv_s2_kernel<.., false>)
-        hipLaunchKernelGGL((dwconv_kernel<bf16_t, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    else
-        hipLaunchKernelGGL((dwconv_kernel<float, false>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    DYK_LAUNCH_CHECK();
-    return DYK_OK;
+    return rc ? rc : dw_launch(d, dw_route_fwd(d), (hipStream_t)stream);
 }
 
 extern "C" int dyk_dwconv_tile_ok(const DykDwDesc* d) {
     const int rc = check_dw(d);
-    if (rc) return rc;
-    if (!(d->stride == 1 && (d->k == 3 || d->k == 5) && (d->dtype == DYK_BF16 || d->dtype == DYK_F16))) return 0;
-    const int K = d->k, TW = 16, IC = TW + K - 1, NLD = K == 5 ? 8 : 6;
-    const int CV = d->C / 8;
-    const int groups = (CV + 7) / 8, CT = (CV + groups - 1) / groups;
-    const int RT = (256 / CT) / 4, IR = RT + K - 1, S = CT | 1;
-    if (IR * IC * CT > NLD * 256) return 0;
-    const size_t lds = (size_t)IR * IC * S * 16 + (size_t)K * K * CT * 8 * 4 + (size_t)CT * 16 * 4;
-    const long nblk = (long)groups * ((d->Wo + TW - 1) / TW) * ((d->Ho + RT - 1) / RT) * d->B;
-    return (nblk < (1L << 31) && lds <= 64 * 1024) ? 1 : 0;
+    return rc ? rc : (dw_fwd_tiled_domain(d) && dw_route_tiled(d, false).rc == DYK_OK ? 1 : 0);
 }
 
 extern "C" int dyk_dwconv_dgrad(const DykDwDesc* d, void* stream) {
     const int rc = check_dw(d);
-    if (rc) return rc;
-    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
-    if (!d->w) return DYK_ERR_ARG;
-    if (d->res) {                    // fused BatchNorm-backward reduce: LDS-tiled kernel only
-        if (!d->bn || !d->stats || d->stats_slots <= 0 || d->ldr < d->C || d->ldr % 8 || ((uintptr_t)d->res % 16)) return DYK_ERR_ARG;
-        if (d->stride != 1 || (d->k != 3 && d->k != 5) || d->dtype != DYK_BF16 || (d->flags & DYK_EW_ACCUM)) return DYK_ERR_UNSUPPORTED;
-        const int rt = d->k == 3 ? launch_dw_tile<3, true>(d, (hipStream_t)stream) : launch_dw_tile<5, true>(d, (hipStream_t)stream);
-        if (rt == DYK_OK) DYK_LAUNCH_CHECK();
-        return rt;
-    }
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
-    int gx, gy;
-    const int CVB = grid2d(d->C / epv, (long)d->B * d->Hi, &gx, &gy, 4096);
-    if (d->stride == 1 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16) {
-        const int rt = d->k == 3 ? launch_dw_tile<3, true>(d, (hipStream_t)stream) : launch_dw_tile<5, true>(d, (hipStream_t)stream);
-        if (rt == DYK_OK) DYK_LAUNCH_CHECK();
-        return rt;
-    }
-    if (d->stride == 2 && (d->k == 3 || d->k == 5) && d->dtype == DYK_BF16) {
-        if (d->k == 3) hipLaunchKernelGGL((dwconv_s2_kernel<bf16_t, 3, true>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-        else hipLaunchKernelGGL((dwconv_s2_kernel<bf16_t, 5, true>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    } else if (d->dtype == DYK_BF16)
-        hipLaunchKernelGGL((dwconv_kernel<bf16_t, true>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    else
-        hipLaunchKernelGGL((dwconv_kernel<float, true>), dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    DYK_LAUNCH_CHECK();
-    return DYK_OK;
-}
-
-template <typename T>
-int launch_dw_wgrad(const DykDwDesc* d, hipStream_t s, int gx, int gy, int CVB) {
-    const dim3 grid(gx, gy, d->k);
-    switch (d->k) {
-    case 1: hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 1>), grid, dim3(256), 0, s, *d, CVB); break;
-    case 3: hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 3>), grid, dim3(256), 0, s, *d, CVB); break;
-    case 5: hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 5>), grid, dim3(256), 0, s, *d, CVB); break;
-    case 7: hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 7>), grid, dim3(256), 0, s, *d, CVB); break;
-    default: return DYK_ERR_UNSUPPORTED;
-    }
-    DYK_LAUNCH_CHECK();
-    return DYK_OK;
+    return rc ? rc : dw_launch(d, dw_route_dgrad(d), (hipStream_t)stream);
 }
 
 extern "C" int dyk_dwconv_wgrad_rows(const DykDwDesc* d) {
     const int rc = check_dw(d);
     if (rc) return rc;
-    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
-    DwWgTile c;
-    if (dw_wgrad_tile_cfg(d, &c)) return c.P;
-    int gx, gy;
-    grid2d(d->C / epv, (long)d->B * d->Ho, &gx, &gy, 768 / d->k);
-    return gy;
+    const DwRoute r = dw_route_wgrad(d);
+    return r.rc != DYK_OK ? r.rc : r.planes;
 }
 
 extern "C" int dyk_dwconv_wgrad(const DykDwDesc* d, void* stream) {
     const int rc = check_dw(d);
     if (rc) return rc;
-    if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
-    if (!d->dw) return DYK_ERR_ARG;
-    const int epv = d->dtype == DYK_BF16 ? 8 : 4;
-    DwWgTile c;
-    if (dw_wgrad_tile_cfg(d, &c)) return launch_dw_wgrad_tile(d, c, (hipStream_t)stream);
-    int gx, gy;
-    // few, long-running workgroups: every workgroup ends with one atomic per (tap, channel) on only k*k*C addresses
-    const int CVB = grid2d(d->C / epv, (long)d->B * d->Ho, &gx, &gy, 768 / d->k);
-    if (d->dtype == DYK_BF16) return launch_dw_wgrad<bf16_t>(d, (hipStream_t)stream, gx, gy, CVB);
-    return launch_dw_wgrad<float>(d, (hipStream_t)stream, gx, gy, CVB);
+    const DwRoute r = dw_route_wgrad(d);
+    if (r.rc == DYK_OK && !d->dw) return DYK_ERR_ARG;
+    return dw_launch(d, r, (hipStream_t)stream);
 }

@@ -482,7 +482,8 @@ int dyk_nhwc_to_nchw(const void* in, float* out, int32_t B, int32_t C, int32_t H
 
 /* ------------------------------------------------------------------------------------
  * Depthwise convolution (nn.Conv2d(groups=C), reference models.py:41 for `groups=` sections and
- * layers.py:223-224 for DepthwiseSeparableConv2d), square kernel k, zero padding `pad`, stride 1 or 2.
+ * layers.py:223-224 for DepthwiseSeparableConv2d), square kernel k <= 7, zero padding `pad`, any stride >= 1 (stride 1 and 2
+ * at k 3 / 5 have kernels of their own, everything else runs on the generic ones).
  * w is the fp32 master weight in tap-major order [k*k][C] (the parameter store layout).
  *   dyk_dwconv_fwd   : y[b,yo,xo,c] = sum_t x[b, yo*s+kh-pad, xo*s+kw-pad, c] * w[t][c]
  *                      stats (optional): replicated fp64 [slots][2][C] sum / sum of squares of y
@@ -523,8 +524,9 @@ typedef struct DykDwDesc {
     int32_t pre_act, _pad;
 } DykDwDesc;
 int dyk_dwconv_fwd(const DykDwDesc* desc, void* stream);
-/* 1 when dyk_dwconv_fwd runs `desc` on the LDS-tiled kernel (stride 1, k in {3, 5}, bf16, tile fits): the precondition of
- * `pre` in the forward and of `res` in the data gradient; 0 otherwise; negative = error code */
+/* 1 when dyk_dwconv_fwd runs a descriptor of this shape on the LDS-tiled kernel (stride 1, k in {3, 5}, bf16 or fp16, tile fits;
+ * `w`, `stats` and `pre` are not looked at): the precondition of `pre` in the forward and, in bf16, of `res` in the data gradient;
+ * 0 otherwise; negative = error code */
 int dyk_dwconv_tile_ok(const DykDwDesc* desc);
 int dyk_dwconv_dgrad(const DykDwDesc* desc, void* stream);
 int dyk_dwconv_wgrad(const DykDwDesc* desc, void* stream);

@@ -32,7 +32,7 @@ CASES = [
     Case("c8_k3p0_5x20", 2, 8, 5, 20, 3, 1, 0, 0, "fdw", True),         # pad 0 at k 3 (pad' = 2)
     Case("c16_k5p2_35x33", 1, 16, 35, 33, 5, 1, 2, 3, "fdw", False),    # CT 2, TH 32: 2 x 3 tiles, several tiles per image
     Case("c4_k3p1_7x9", 2, 4, 7, 9, 3, 1, 1, 1, "fdw", True),           # fp32 only: one float4 vector
-    # ---- stride 2: generic forward, dwconv_s2_kernel data gradient (bf16), row weight gradient per-pixel path
+    # ---- stride 2: generic forward, dwconv_s2_dgrad_kernel data gradient (bf16), row weight gradient per-pixel path
     Case("c12_k5p2s2_9x8", 1, 12, 9, 8, 5, 2, 2, 3, "fdw", False),      # fp32 only, three float4 vectors; Hi odd, Wi even
     Case("c264_k3p1s2_9x12", 1, 264, 9, 12, 3, 2, 1, 1, "fdw", True),   # CVB 32: second channel block with ONE active vector; Hi odd, Wi even
     Case("c24_k3p0s2_8x10", 2, 24, 8, 10, 3, 2, 0, 0, "fdw", False),    # pad 0, Hi and Wi even: the last row AND column get no gradient

@@ -146,7 +146,7 @@ DEAD = [c for c in CASES if "d" in c.ops and max(dead_tail(c)) > 0]
 
 
 def test_matrix_has_rows_and_columns_without_gradient():
-    """stride 2 at k 3 and k 5 (dwconv_s2_kernel), and stride 3 (generic kernel)"""
+    """stride 2 at k 3 and k 5 (dwconv_s2_dgrad_kernel), and stride 3 (generic kernel)"""
     assert {(c.k, c.s) for c in DEAD if dead_tail(c)[0]} >= {(3, 2), (5, 2), (3, 3)}
     assert {(c.k, c.s) for c in DEAD if dead_tail(c)[1]} >= {(3, 2), (5, 2)}
     for c in CASES:

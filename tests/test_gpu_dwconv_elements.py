@@ -17,8 +17,8 @@ Kernel instantiations dwconv.hip launches, and a case that reaches each (bf16 un
     dwconv_tile_kernel<5, fwd, bf16>    c24_k5p2_23x17, c64_k5p1_9x3, c264_k5p0_6x21, c16_k5p2_35x33; `pre` k 5
     dwconv_tile_kernel<3 | 5, fwd, f16> the same cases in f16
     dwconv_tile_kernel<3 | 5, grad>     the same cases, data gradient (pad' = k - 1 - pad: 1, 2 at k 3; 2, 3, 4 at k 5)
-    dwconv_s2_kernel<bf16, 3, grad>     c264_k3p1s2_9x12, c24_k3p0s2_8x10 (last row and column exact zeros), c8_k3p2s2_6x5
-    dwconv_s2_kernel<bf16, 5, grad>     c72_k5p2s2_11x10, c16_k5p0s2_10x10 (last row and column exact zeros), c8_k5p1s2_9x12
+    dwconv_s2_dgrad_kernel<3, bf16>     c264_k3p1s2_9x12, c24_k3p0s2_8x10 (last row and column exact zeros), c8_k3p2s2_6x5
+    dwconv_s2_dgrad_kernel<5, bf16>     c72_k5p2s2_11x10, c16_k5p0s2_10x10 (last row and column exact zeros), c8_k5p1s2_9x12
     dwconv_wgrad_kernel<bf16, 1>        c72_k1_5x9                       (strip path)
     dwconv_wgrad_kernel<bf16, 3>        c264_k3p1s2_9x12, c24_k3p0s2_8x10, c8_k3p2s2_6x5, c24_k3p1s3_12x11; `pre` stride 2   (per-pixel path)
     dwconv_wgrad_kernel<bf16, 5>        c72_k5p2s2_11x10, c16_k5p0s2_10x10, c8_k5p1s2_9x12; `pre` stride 2                    (per-pixel path)
@@ -186,7 +186,7 @@ def test_data_gradient(case_id, dt, accumulate):
 
 def _wgrad_geometry(c):
     """(tiles, channel groups, workgroups per channel group = planes) of the persistent tiled weight gradient: at most 512
-    workgroups per launch, the tiles dealt evenly over the rounds (dw_wgrad_tile_cfg)"""
+    workgroups per launch, the tiles dealt evenly over the rounds (dw_route_wgrad)"""
     cv = c.C // 8
     groups = (cv + 7) // 8
     ct = -(-cv // groups)
@@ -199,7 +199,7 @@ def _wgrad_geometry(c):
 
 
 def _wgrad_row_planes(c, dt):
-    """workgroup rows (= planes) of the row kernel: image rows of the output, capped at 768 / k workgroups per launch (grid2d)"""
+    """workgroup rows (= planes) of the row kernel: image rows of the output, capped at 768 / k workgroups per launch (dw_route_rows)"""
     cv = c.C // (4 if dt == "f32" else 8)
     cvb = 1
     while cvb < cv and cvb < 32:
