@@ -299,8 +299,10 @@ _ACT_D = {
     "hard-swish": (lambda t: torch.where(t < -3, 0.0, torch.where(t <= 3, t / 3 + 0.5, 1.0)).to(_F64), [(-3.0, 0.5), (3.0, 0.5)],
                    lambda t, e_t: torch.where(t.abs() <= 3 + e_t, e_t / 3 + 2 * U * (t.abs() / 3 + 0.5), torch.zeros_like(t))),
     "mish": (_mish_d, [], _mish_err),
+    # (x > -3 && x < 3) ? 1 / 6f : 0 -- strict on both sides, the rounded constant
+    "hard-sigmoid": (lambda t: ((t > -3) & (t < 3)).to(_F64) / 6.0, [(-3.0, 1.0 / 6.0), (3.0, 1.0 / 6.0)], lambda t, e_t: torch.full_like(t, U / 6.0)),
 }
-REDUCE_ACTS = list(_ACT_D)
+REDUCE_ACTS = ["linear", "leaky", "relu", "relu6", "hard-swish", "mish"]      # what the reduce riding on dyk_se_scale is run with
 
 
 def se_reduce(g, yraw, vecs, act, m):

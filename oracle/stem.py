@@ -23,7 +23,8 @@ Bounds, u = 2^-24.
                         |s1 - S1| <= sum e + n u sum|y|,  |s2 - S2| <= sum (2|y|e + e^2 + u y^2) + n u sum y^2
   eval epilogue         z = act(t), t = y*scale + shift:  e_t = |scale| e + 2u (|y*scale| + |shift|),  e_z = L_act e_t + a_act
                         L_act the largest slope (1 linear, leaky, relu6; 1.5 hard-swish; 1.09 mish), a_act the activation's own
-                        evaluation error: 0 linear and relu6, u|z| leaky, 4u|z| hard-swish, and for mish as act_fwd writes it
+                        evaluation error: 0 linear and relu6, u|z| leaky, 4u|z| hard-swish (relu and hard-sigmoid, which the stem's
+                        cases do not run: see the table below and oracle/bn_act.py), and for mish as act_fwd writes it
                         (e = __expf(min(t, 20)), n = e (e + 2), t * n * rcp(n + 2))  a_act = (2 (|t| + 4) + 4) u |z|: the argument
                         scaling of the exponential, |t| u, plus 1 ulp each for v_exp_f32 and v_rcp_f32 carried through n / (n + 2).
                         Then the storage rule with e_z.
@@ -47,15 +48,20 @@ _F64 = torch.float64
 ACC_ULPS = 88.0
 AMBIGUOUS_SHARE = 0.01
 
-# activation -> (largest slope, own evaluation error as a function of (t, z) in units of u)
+# activation -> (largest slope, own evaluation error as a function of (t, z) in units of u).  The one table of the forward activations: the
+# stem suite runs ACTS, the BatchNorm/activation suite (oracle/bn_act.py) all seven.  relu is a selection (no arithmetic); hard-sigmoid
+# is fminf(fmaxf(t + 3, 0), 6) * (1 / 6f): the add (u |t + 3|, carried through the slope 1/6), the rounded constant and the product.
 _ACT = {
     "linear": (1.0, lambda t, z: torch.zeros_like(z)),
     "leaky": (1.0, lambda t, z: z.abs()),
     "relu6": (1.0, lambda t, z: torch.zeros_like(z)),
     "hard-swish": (1.5, lambda t, z: 4.0 * z.abs()),
     "mish": (1.09, lambda t, z: (2.0 * (t.abs() + 4.0) + 4.0) * z.abs()),
+    "relu": (1.0, lambda t, z: torch.zeros_like(z)),
+    "hard-sigmoid": (1.0 / 6.0, lambda t, z: (t + 3.0).abs() / 6.0 + 2.0 * z.abs()),
 }
-ACTS = list(_ACT)
+ACTS = ["linear", "leaky", "relu6", "hard-swish", "mish"]          # what the stem's eval epilogue is run with
+ALL_ACTS = list(_ACT)
 
 
 def act64(name, t):
@@ -66,6 +72,10 @@ def act64(name, t):
         return torch.where(t > 0, t, 0.1 * t)
     if name == "relu6":
         return t.clamp(0.0, 6.0)
+    if name == "relu":
+        return t.clamp(min=0.0)
+    if name == "hard-sigmoid":
+        return (t + 3.0).clamp(0.0, 6.0) / 6.0
     if name == "hard-swish":
         return t * (t + 3.0).clamp(0.0, 6.0) / 6.0
     if name == "mish":
