@@ -205,6 +205,28 @@ class DykEmaDesc(ctypes.Structure):
                 ("nregions", _i32), ("d", _f32), ("omd", _f32)]
 
 
+TSTAT_MAX_BUFS = 4         # DYK_TSTAT_MAX_BUFS (include/dyk_hip.h): buffers of one dyk_tensor_stats call
+TSTAT_ITEM = 4096          # DYK_TSTAT_ITEM: elements per work item
+
+
+class DykTensorSeg(ctypes.Structure):
+    _fields_ = [("offset", _i64), ("numel", _i64), ("flags", ctypes.c_uint32), ("item_begin", _i32)]
+
+
+class DykTensorItem(ctypes.Structure):
+    _fields_ = [("first", _i64), ("seg", _i32), ("len", _i32)]
+
+
+class DykTensorStat(ctypes.Structure):
+    _fields_ = [("sumsq", ctypes.c_double), ("absmax", _f32), ("nonfinite", ctypes.c_uint32), ("zeros", ctypes.c_uint32),
+                ("_pad", ctypes.c_uint32)]
+
+
+class DykTensorStatsDesc(ctypes.Structure):
+    _fields_ = [("buf", _vp * TSTAT_MAX_BUFS), ("seg", _vp), ("items", _vp), ("ws", _vp), ("out", _vp), ("n", _i64),
+                ("ws_bytes", _i64), ("nbuf", _i32), ("nseg", _i32), ("nitems", _i32), ("_pad", _i32)]
+
+
 class DykNmsDesc(ctypes.Structure):
     _fields_ = [("pred", _vp), ("out", _vp), ("out_rows", _vp), ("counts", _vp), ("ws", _vp), ("ws_per_image", _i64),
                 ("B", _i32), ("N", _i32), ("no", _i32), ("conf_thres", _f32), ("iou_thres", _f32),
@@ -289,6 +311,8 @@ SIGNATURES = {
     "dyk_adam_step_groups": (_i32, [_P(DykOptimDesc), _P(DykOptimGroups), _vp, _vp]),
     "dyk_sgd_step_groups": (_i32, [_P(DykOptimDesc), _P(DykOptimGroups), _vp, _vp]),
     "dyk_ema_update": (_i32, [_P(DykEmaDesc), _vp]),
+    "dyk_tensor_stats_ws_bytes": (_i64, [_i64, _i32]),
+    "dyk_tensor_stats": (_i32, [_P(DykTensorStatsDesc), _vp]),
     "dyk_run_commands_timed": (_i32, [_P(DykCommand), _i32, _vp, _P(_f32)]),
     "dyk_loss_scale_grads": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "dyk_loss_scale_grads3": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),

@@ -396,6 +396,93 @@ def grad_stats(g, rec, ws, *, mask=None, grad_scale=1.0, max_norm=0.0, beta1=0.0
     call("dyk_grad_stats", d)
 
 
+# --------------------------------------------------------------------------- per-tensor statistics (csrc/tensor_stats.hip)
+TSTAT_BYTES = ctypes.sizeof(_l.DykTensorStat)
+
+
+def _tstat_dtypes():
+    import numpy as np
+    seg = np.dtype([("offset", "<i8"), ("numel", "<i8"), ("flags", "<u4"), ("item_begin", "<i4")])
+    item = np.dtype([("first", "<i8"), ("seg", "<i4"), ("len", "<i4")])
+    stat = np.dtype([("sumsq", "<f8"), ("absmax", "<f4"), ("nonfinite", "<u4"), ("zeros", "<u4"), ("_pad", "<u4")])
+    assert (seg.itemsize, item.itemsize, stat.itemsize) == tuple(
+        ctypes.sizeof(c) for c in (_l.DykTensorSeg, _l.DykTensorItem, _l.DykTensorStat))
+    return seg, item, stat
+
+
+def tensor_stats_tables(segments):
+    """[(offset, numel, flags)] in elements -> (DykTensorSeg[nseg], DykTensorItem[nitems]) as numpy structured arrays: every
+    segment, in table order, cut into items of 4096 elements (the last one shorter); seg.item_begin names its first item.
+    Offsets are multiples of 4, numels >= 1 (include/dyk_hip.h)."""
+    import numpy as np
+    seg_t, item_t, _ = _tstat_dtypes()
+    if not len(segments):
+        raise ValueError("an empty segment table")
+    arr = np.asarray([tuple(int(x) for x in s) for s in segments], dtype=np.int64).reshape(-1, 3)
+    off, numel, flags = arr[:, 0], arr[:, 1], arr[:, 2]
+    if (off < 0).any() or (off % 4).any() or (numel < 1).any():
+        raise ValueError("segments start at multiples of 4 elements and hold at least one element")
+    if (flags < 0).any() or (flags >> _l.TSTAT_MAX_BUFS).any():
+        raise ValueError("segment flags: one skip bit per buffer, %d buffers at the most" % _l.TSTAT_MAX_BUFS)
+    cnt = (numel + _l.TSTAT_ITEM - 1) // _l.TSTAT_ITEM
+    begin = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+    if int(cnt.sum()) > 2 ** 31 - 1:
+        raise ValueError("too many work items")
+    segs = np.zeros(len(arr), seg_t)
+    segs["offset"], segs["numel"], segs["flags"], segs["item_begin"] = off, numel, flags, begin
+    which = np.repeat(np.arange(len(arr)), cnt)
+    j = np.arange(int(cnt.sum())) - begin[which]
+    items = np.zeros(len(which), item_t)
+    items["first"] = off[which] + j * _l.TSTAT_ITEM
+    items["seg"] = which
+    items["len"] = np.minimum(numel[which] - j * _l.TSTAT_ITEM, _l.TSTAT_ITEM)
+    return segs, items
+
+
+def tensor_stats_worklist(segments, device):
+    """the segment table and its work list on `device`, the workspace that goes with them for `nbuf` buffers on demand:
+    -> dict(seg, items: uint8 device tensors, nseg, nitems, extent = elements the segments reach).  Built once per table."""
+    segs, items = tensor_stats_tables(segments)
+    dev = lambda a: torch.frombuffer(bytearray(a.tobytes()), dtype=torch.uint8).to(device)
+    return dict(seg=dev(segs), items=dev(items), nseg=len(segs), nitems=len(items),
+                extent=int((segs["offset"] + segs["numel"]).max()))
+
+
+def tensor_stats_workspace(nitems, nbuf, device):
+    return torch.empty(int(load().dyk_tensor_stats_ws_bytes(nitems, nbuf)), dtype=torch.uint8, device=device)
+
+
+def tensor_stats(bufs, table, out, ws, n=None):
+    """per-(segment, buffer) {sumsq, absmax, nonfinite, zeros} of the flat fp32 buffers `bufs` (1..4, one layout) into
+    `out` (uint8, nseg * len(bufs) * 24 bytes); `table` from tensor_stats_worklist, `ws` from tensor_stats_workspace.
+    Two launches on the current stream, no synchronisation."""
+    bufs = list(bufs)
+    _require_cuda(out, ws, table["seg"], table["items"], *bufs)
+    if not 1 <= len(bufs) <= _l.TSTAT_MAX_BUFS:
+        raise _l.DykError("dyk_tensor_stats takes 1 to %d buffers, got %d" % (_l.TSTAT_MAX_BUFS, len(bufs)))
+    n = min(b.numel() for b in bufs) // 4 * 4 if n is None else n
+    for b in bufs:
+        if b.dtype != torch.float32 or not b.is_contiguous():
+            raise _l.DykError("dyk_tensor_stats reads contiguous float32 buffers (got %s)" % b.dtype)
+    if table["extent"] > n:
+        raise _l.DykError("the segment table reaches element %d of buffers of %d" % (table["extent"], n))
+    if out.numel() * out.element_size() < table["nseg"] * len(bufs) * TSTAT_BYTES:
+        raise _l.DykError("dyk_tensor_stats: the output holds fewer than nseg * nbuf records")
+    d = _l.DykTensorStatsDesc()
+    for k, b in enumerate(bufs):
+        d.buf[k] = b.data_ptr()
+    d.seg, d.items, d.ws, d.out = table["seg"].data_ptr(), table["items"].data_ptr(), ws.data_ptr(), out.data_ptr()
+    d.n, d.ws_bytes = n, ws.numel() * ws.element_size()
+    d.nbuf, d.nseg, d.nitems = len(bufs), table["nseg"], table["nitems"]
+    call("dyk_tensor_stats", d)
+
+
+def tensor_stats_records(host_bytes, nseg, nbuf):
+    """numpy structured array [nseg][nbuf] of DykTensorStat from a host copy of the output"""
+    import numpy as np
+    return np.frombuffer(bytes(host_bytes), dtype=_tstat_dtypes()[2], count=nseg * nbuf).reshape(nseg, nbuf)
+
+
 def _step_guarded(name, desc, rec):
     check(getattr(load(), name)(ctypes.byref(desc), _ptr(rec), _stream()), name)
 

@@ -81,6 +81,19 @@ class ParamStore:
         key (their weight gradients are not computed) and of the fused optimizers' update mask"""
         return tuple(e.name for e in self.entries if not e.param.requires_grad)
 
+    def segment_table(self):
+        """the layout of the flat buffers as segments for dyk_tensor_stats (dyk/monitor.py) -> (params, running):
+        params  : [(name, offset, numel)] one per Entry, in store order, over P / G and the fused optimizers' flat moments;
+                  the names are those of model.named_parameters()
+        running : the same for the BatchNorm running statistics over R, named as in model.named_buffers()"""
+        params = [(e.name, e.offset, e.numel) for e in self.entries]
+        owner = {}
+        for li, mod in enumerate(self.model.module_list):
+            for mname, sub in mod.named_modules():
+                owner[id(sub)] = "module_list.%d.%s" % (li, (mname + ".") if mname else "")
+        running = [(owner[id(m)] + attr, roff, n) for (m, attr, roff, n) in self.rstats]
+        return params, running
+
     # ------------------------------------------------------------------ adoption
     def _view(self, flat, e):
         s = flat[e.offset:e.offset + e.numel].view(e.storage_shape)

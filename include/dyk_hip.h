@@ -914,6 +914,88 @@ typedef struct DykEmaDesc {
 int dyk_ema_update(const DykEmaDesc* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Per-tensor statistics of up to DYK_TSTAT_MAX_BUFS flat fp32 buffers that share one segment table (the parameter store P,
+ * its gradient G and the fused optimizers' flat moments; replaces a host loop of `p.grad.norm()` / `torch.isfinite(p.grad)`
+ * over some 600 views, each with its own kernels and a `.item()` synchronisation).  A segmented reduction in two launches; no
+ * atomics and no in-launch hand-off: the kernel boundary orders the partials before the fold.
+ *
+ * Segment s is the elements [offset, offset + numel) of every buffer: offset a multiple of 4 (16-byte vector loads hold; the
+ * parameter store gives multiples of 64), numel >= 1 and NOT necessarily a multiple of 4.  What lies between segments is never
+ * read into any field (the 16-byte vector that holds a segment's last elements is loaded whole and masked per element).
+ * flags bit k (k < nbuf) : segment s is skipped for buffer k -- buf[k] is not read there and out[s][k] is written as all zeros
+ * (frozen parameters have neither gradient nor moments).
+ * The work list cuts every segment, in table order, into items of DYK_TSTAT_ITEM = 4096 elements (the last one shorter):
+ *   item i = {first = offset + 4096 * j, seg = s, len}  for j = 0 .. ceil(numel / 4096) - 1,   seg[s].item_begin = index of j = 0
+ * It is a function of the table only; the caller builds it once per table and keeps both on the device (dyk.ops.
+ * tensor_stats_worklist).  An item never crosses a segment.
+ *
+ * Per (segment, buffer) -- DykTensorStat:
+ *   sumsq     : sum of x*x over the FINITE elements, in fp64.  Each x*x is exact in fp64 (two 24-bit significands); a
+ *               non-finite element contributes an exact 0.
+ *   absmax    : max of |x| over the finite elements, 0 when there is none.  Exact.
+ *   nonfinite : elements with !(|x| <= FLT_MAX) (inf, NaN).  Exact; saturates at 2^32 - 1.
+ *   zeros     : elements equal to +0.0 or -0.0.  Exact; saturates at 2^32 - 1.
+ *
+ * dyk_tensor_stats : two launches on `stream`:
+ *   partials : one workgroup of 256 threads per item (grid = nitems), all nbuf buffers in the same pass.  Thread t takes the
+ *              16-byte vectors t, t + 256, t + 512, t + 768 of the item, in that order, and the four elements of a vector in
+ *              order; elements at or past `len` are left out.  Per buffer the thread adds x*x (0 for a non-finite x) to an
+ *              fp64 accumulator that starts at +0.0, one fused multiply-add per element (one rounding: the product is exact).
+ *              The 64 lanes of a wave fold as l += l+32, l+16, l+8, l+4, l+2, l+1; the four waves add in order
+ *              ((w0 + w1) + w2) + w3.  One partial {sumsq, absmax, nonfinite, zeros} per (item, buffer) goes to
+ *              ws[item * nbuf + k] (dyk_tensor_stats_ws_bytes(nitems, nbuf) bytes, 8-byte aligned).
+ *   fold     : one wave per segment (workgroups of 4 waves, grid = ceil(nseg / 4)).  With b = seg[s].item_begin and
+ *              c = ceil(numel / 4096), lane l adds the partials b + l, b + l + 64, b + l + 128, ... (< b + c) in that order to
+ *              an accumulator that starts at +0.0; the lanes fold as above; lane 0 writes out[s * nbuf + k].
+ *   Every addition adds values >= 0, so adding the exact zeros of absent elements / partials changes no bit: sumsq is a
+ *   function of (buffers, table) only, bit-identical from run to run and independent of grid size and arrival order, and a
+ *   restatement that performs these additions in this order (tests/tensor_stats_ref.py) reproduces it bit for bit.
+ *   absmax and the counts are exact in any order.
+ * Argument contract: buf[0..nbuf) 16-byte aligned, each of n elements, n a positive multiple of 4; every segment inside
+ * [0, n); seg, items, ws and out 8-byte aligned; 1 <= nbuf <= DYK_TSTAT_MAX_BUFS; nseg >= 1; nitems >= nseg;
+ * ws_bytes >= dyk_tensor_stats_ws_bytes(nitems, nbuf).  Otherwise (or with a NULL descriptor / buffer / table / work list /
+ * workspace / output) DYK_ERR_ARG before any launch.  The tables live in device memory, so the kernels check them: an item
+ * that names a segment outside the table, is longer than 4096, does not lie inside its segment or inside [0, n), and a
+ * segment whose items do not lie inside the work list, read nothing and contribute zeros.
+ * dyk_tensor_stats_ws_bytes(nitems, nbuf) : bytes of workspace, 0 for arguments out of range.
+ * ---------------------------------------------------------------------------------- */
+#define DYK_TSTAT_MAX_BUFS 4
+#define DYK_TSTAT_ITEM 4096
+typedef struct DykTensorSeg {
+    int64_t offset;        /* first element, a multiple of 4 */
+    int64_t numel;         /* >= 1 */
+    uint32_t flags;        /* bit k: skipped for buffer k */
+    int32_t item_begin;    /* index of the segment's first item in the work list */
+} DykTensorSeg;
+typedef struct DykTensorItem {
+    int64_t first;         /* first element of the item in the buffers (seg.offset + 4096 * j) */
+    int32_t seg;
+    int32_t len;           /* 1 .. 4096 */
+} DykTensorItem;
+typedef struct DykTensorStat {
+    double sumsq;
+    float absmax;
+    uint32_t nonfinite;
+    uint32_t zeros;
+    uint32_t _pad;         /* written as 0 */
+} DykTensorStat;
+typedef struct DykTensorStatsDesc {
+    const float* buf[DYK_TSTAT_MAX_BUFS];
+    const DykTensorSeg* seg;       /* device, [nseg] */
+    const DykTensorItem* items;    /* device, [nitems] */
+    void* ws;                      /* device, dyk_tensor_stats_ws_bytes(nitems, nbuf) bytes */
+    DykTensorStat* out;            /* device, [nseg][nbuf] */
+    int64_t n;                     /* elements of every buffer */
+    int64_t ws_bytes;
+    int32_t nbuf;
+    int32_t nseg;
+    int32_t nitems;
+    int32_t _pad;
+} DykTensorStatsDesc;
+int64_t dyk_tensor_stats_ws_bytes(int64_t nitems, int32_t nbuf);
+int dyk_tensor_stats(const DykTensorStatsDesc* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Stem convolution (Cin = 3, 3x3, pad 1, stride 1 | 2, Cout 16 | 32) straight from the image batch, no im2col.
  * Replaces `imgs.float() / 255.0` (train_utils/kaist_train_eval_utils.py:54-55, evaluate.py:67-68) + nn.Conv2d(3, C, 3)
  * of module_list[0] / module_list[second_index] (models.py:34-42) and that layer's weight gradient.
