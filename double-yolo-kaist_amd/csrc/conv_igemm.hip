@@ -2,16 +2,7 @@
 // instantiation (conv_igemm_n{80,128,160}.hip; kernel in conv_igemm_kernel.h).
 #include <stddef.h>
 #include <string.h>
-#include "dyk_common.h"
-
-int dyk_conv_launch_n128(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n80(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n160(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_halo(const DykConvDesc* d, hipStream_t s, int th);
-int dyk_conv_launch_kg(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_lt(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_sc(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_pw(const DykConvDesc* d, hipStream_t s);
+#include "conv_tune.h"
 
 static int conv_validate(const DykConvDesc* d) {
     if (!d || !d->x || !d->w || !d->y) return DYK_ERR_ARG;
@@ -63,6 +54,7 @@ static int conv_validate(const DykConvDesc* d) {
     return DYK_OK;
 }
 
+// validate, route (conv_tune.h), try the family; a family that refuses the problem hands it to its generic tile
 extern "C" int dyk_conv_igemm(const DykConvDesc* d, void* stream) {
     int rc0 = conv_validate(d);
     if (rc0 != DYK_OK) return rc0;
@@ -73,88 +65,69 @@ extern "C" int dyk_conv_igemm(const DykConvDesc* d, void* stream) {
         if (memcmp((const char*)d + lo, (const char*)d->twin + lo, hi - lo) != 0) return DYK_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-    const int tile = d->dtype != DYK_F32 ? (d->tune >> 12) & 0xf : 0;      // 80 / 160 pixel tiles are built for the 16-bit types only
-    if (d->flags & DYK_EPI_BNFWD) {        // generic tiles only (the halo / K-grouped kernels do not carry this epilogue)
-        if (tile == 1 || tile == 3) return dyk_conv_launch_n80(d, s);
-        if (tile == 2 || tile == 4) return dyk_conv_launch_n160(d, s);
-        return dyk_conv_launch_n128(d, s);
-    }
-    if (tile == 5) {                       // large-tile 3x3 kernels (conv_lt_kernel.h); generic 160-pixel tiles where they do not apply
-        const int rc = dyk_conv_launch_lt(d, s);
-        if (rc != DYK_ERR_UNSUPPORTED || ((d->tune >> 23) & 1)) return rc;       // (bit 23, analysis: no fallback)
-        return dyk_conv_launch_n160(d, s);
-    }
-    if (tile == 6) {                       // resident-weight 3x3 data gradient into 32-channel tensors (conv_sc.hip)
-        const int rc = (d->splitk > 1 || d->dtype != DYK_BF16) ? DYK_ERR_UNSUPPORTED : dyk_conv_launch_sc(d, s);
-        if (rc != DYK_ERR_UNSUPPORTED || ((d->tune >> 23) & 1)) return rc;       // (bit 23, analysis: no fallback)
-        return dyk_conv_launch_n128(d, s);
-    }
-    if (tile == 7) {                       // persistent resident-weight pointwise kernels (conv_pw_kernel.h)
-        const int rc = dyk_conv_launch_pw(d, s);
-        if (rc != DYK_ERR_UNSUPPORTED || ((d->tune >> 23) & 1)) return rc;       // (bit 23, analysis: no fallback)
-        return dyk_conv_launch_n128(d, s);
-    }
-    if (((d->tune >> 28) & 7) == 1) {      // K-grouped workgroups (conv_igemm_kg.hip); generic tiles where they do not apply
-        const int rc = dyk_conv_launch_kg(d, s);
-        if (rc != DYK_ERR_UNSUPPORTED || ((d->tune >> 23) & 1)) return rc;       // (bit 23, analysis: no fallback)
-    }
-    if (tile == 3 || tile == 4) {          // 3x3 halo kernel; falls back to the generic tiles when the problem does not fit it
-        const int rc = dyk_conv_launch_halo(d, s, tile == 3 ? 4 : 8);
-        if (rc != DYK_ERR_UNSUPPORTED || ((d->tune >> 23) & 1)) return rc;       // (bit 23, analysis: no fallback)
-        return tile == 3 ? dyk_conv_launch_n80(d, s) : dyk_conv_launch_n160(d, s);
-    }
-    if (tile == 1) return dyk_conv_launch_n80(d, s);
-    if (tile == 2) return dyk_conv_launch_n160(d, s);
-    return dyk_conv_launch_n128(d, s);
+    auto launch = [&](int family) {
+        switch (family) {
+        case CONV_N80: return dyk_conv_launch_n80(d, s);
+        case CONV_N160: return dyk_conv_launch_n160(d, s);
+        case CONV_HALO4: return dyk_conv_launch_halo(d, s, 4);
+        case CONV_HALO8: return dyk_conv_launch_halo(d, s, 8);
+        case CONV_LT: return dyk_conv_launch_lt(d, s);
+        // (resident-weight data gradient: bf16 without split-K only)
+        case CONV_SC: return (d->splitk > 1 || d->dtype != DYK_BF16) ? (int)DYK_ERR_UNSUPPORTED : dyk_conv_launch_sc(d, s);
+        case CONV_PW: return dyk_conv_launch_pw(d, s);
+        case CONV_KG: return dyk_conv_launch_kg(d, s);
+        default: return dyk_conv_launch_n128(d, s);
+        }
+    };
+    const ConvRoute r = conv_route(d);
+    const int rc = r.family < 0 ? r.family : launch(r.family);
+    return (rc != DYK_ERR_UNSUPPORTED || r.fallback < 0 || conv_tune_nofallback(d->tune)) ? rc : launch(r.fallback);
+}
+
+extern "C" int dyk_conv_route(const DykConvDesc* d, int32_t* fallback_tile) {
+    const ConvRoute r = d ? conv_route(d) : ConvRoute{DYK_ERR_ARG, -1};
+    if (fallback_tile) *fallback_tile = r.fallback;
+    return r.family;
 }
 
 extern "C" int dyk_conv_bnfwd_max_grid(void) { return 256; }
 
-// workgroups of the generic-tile launch of `d` (the tile selection of dispatch_conv_bn; halo / K-grouped launches differ)
+// workgroups of the generic-tile launch of `d`: of the tile DYK_EPI_BNFWD runs for its tune word, whatever the flags of `d`
+// (halo / K-grouped / large-tile launches differ)
 extern "C" int dyk_conv_grid(const DykConvDesc* d) {
     if (!d || d->B <= 0 || d->Hg <= 0 || d->Wg <= 0 || d->Cout <= 0) return DYK_ERR_ARG;
-    const int tile = d->dtype != DYK_F32 ? (d->tune >> 12) & 0xf : 0;
-    const int bn = (tile == 1 || tile == 3) ? 80 : ((tile == 2 || tile == 4) ? 160 : 128);
-    int bm = d->Cout > 64 ? 128 : (d->Cout > 32 ? 64 : 32);
-    const int bm_code = (d->tune >> 24) & 0xf;
-    if (bm_code >= 1 && bm_code <= 3) bm = 16 << bm_code;
-    if (bn == 80 && bm == 32) bm = 64;
+    const ConvTile t = conv_generic_tile(d, conv_route_bnfwd(d), false);
     const long n = (long)d->B * d->Hg * d->Wg;
-    return (int)((n + bn - 1) / bn) * ((d->Cout + bm - 1) / bm) * (d->ncls > 1 ? d->ncls : 1);
+    return (int)((n + t.bn - 1) / t.bn) * ((d->Cout + t.bm - 1) / t.bm) * (d->ncls > 1 ? d->ncls : 1);
 }
 
-// split-K scratch: bytes of sk_ws and words of sk_cnt that hold for every kernel the tune word of `d` can select (the chosen
-// kernel AND the generic tile it falls back to): S * 4 bytes * (Cout rounded up to the channel tile) * (positions rounded up
-// to the pixel tile), tiles = their product counted in tiles
+// split-K scratch: bytes of sk_ws and words of sk_cnt that hold for every kernel the route of `d` can run (the family AND the
+// generic tile it falls back to): S * 4 bytes * (Cout rounded up to the channel tile) * (positions rounded up to the pixel
+// tile), tiles = their product counted in tiles
 extern "C" int64_t dyk_conv_splitk_ws_bytes(const DykConvDesc* d, int32_t* tiles) {
     if (tiles) *tiles = 0;
     if (!d || d->B <= 0 || d->Hg <= 0 || d->Wg <= 0 || d->Cout <= 0) return DYK_ERR_ARG;
     if (d->splitk <= 1) return 0;
+    // (DYK_EPI_BNFWD excludes split-K, conv_validate: under that flag the route is the generic one and the answer is moot)
+    ConvRoute r = conv_route(d);
+    if (r.family < 0) r = conv_route_bnfwd(d);                            // (a word no kernel runs: its generic tile)
     const long n = (long)d->B * d->Hg * d->Wg;
-    const int tile = d->dtype != DYK_F32 ? (d->tune >> 12) & 0xf : 0;
     int64_t bytes = 0;
     int32_t nt = 0;
-    auto cover = [&](int bm, int bn) {
-        const int64_t tm = (d->Cout + bm - 1) / bm, tn = (n + bn - 1) / bn;
-        const int64_t b = tm * tn * (int64_t)d->splitk * bm * bn * 4;
+    auto cover = [&](ConvTile t) {
+        const int64_t tm = (d->Cout + t.bm - 1) / t.bm, tn = (n + t.bn - 1) / t.bn;
+        const int64_t b = tm * tn * (int64_t)d->splitk * t.bm * t.bn * 4;
         if (b > bytes) bytes = b;
         if (tm * tn > nt) nt = (int32_t)(tm * tn);
     };
-    // generic tile (also the fallback of the large-tile / halo / resident-weight codes)
-    {
-        const int bn = (tile == 1 || tile == 3) ? 80 : ((tile == 2 || tile == 4 || tile == 5) ? 160 : 128);
-        int bm = d->Cout > 64 ? 128 : (d->Cout > 32 ? 64 : 32);
-        const int bm_code = (d->tune >> 24) & 0xf;
-        if (tile != 5 && bm_code >= 1 && bm_code <= 3) bm = 16 << bm_code;
-        if (bn == 80 && bm == 32) bm = 64;
-        if (((d->tune >> 28) & 7) == 1 && bm < 64) bm = 64;
-        cover(bm, bn);
-    }
-    if (tile == 5) {
-        const int shape = (d->tune >> 8) & 0xf;
-        if (shape == 1) cover(128, 320);
-        else if (shape == 2) cover(256, 160);
-        else cover(128, 160);
+    // the generic tile as the word's channel code reads; under the K-grouped bit at least 64 rows, whichever kernel takes it.
+    // (K-grouped with channel code 1 and Cout > 64 launches 128 rows, which this does not cover: launch_conv_impl refuses it)
+    ConvTile g = conv_generic_tile(d, r, false);
+    if (conv_tune_kgrouped(d->tune) && g.bm < 64) g.bm = 64;
+    cover(g);
+    if (r.family == CONV_LT) {
+        const int shape = conv_tune_lt_shape(d->tune);
+        cover(shape == 1 ? ConvTile{128, 320} : (shape == 2 ? ConvTile{256, 160} : ConvTile{128, 160}));
     }
     if (tiles) *tiles = nt;
     return bytes;

@@ -1,8 +1,6 @@
 // Instantiations of the 3x3 halo-tile convolution (kernel in conv_igemm_kernel.h).
 #include "conv_igemm_kernel.h"
 
-int dyk_conv_launch_halob(const DykConvDesc* d, hipStream_t s, int th);
-int dyk_conv_launch_haloh(const DykConvDesc* d, hipStream_t s, int th);
 int dyk_conv_launch_halo(const DykConvDesc* d, hipStream_t s, int th) {
     if (d->dtype == DYK_F16) return dyk_conv_launch_haloh(d, s, th);
     if (d->dtype != DYK_BF16) return DYK_ERR_UNSUPPORTED;

@@ -21,7 +21,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
-#include "dyk_common.h"
+#include "conv_tune.h"
 
 namespace {
 
@@ -175,8 +175,8 @@ __device__ __forceinline__ void conv_epilogue(const DykConvDesc& desc, f32x4_t (
     constexpr int MI = WTM / 16, NI = WTN / 16;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WN, wn = wid % WN;
-    const bool abl_nostore = (a.tune >> 16) & 1;
-    if ((a.tune >> 20) & 1) {                  // ablation: no epilogue (keep the accumulators alive)
+    const bool abl_nostore = conv_tune_abl_nostore(a.tune);
+    if (conv_tune_abl_noepi(a.tune)) {                  // ablation: no epilogue (keep the accumulators alive)
         float sum = 0.f;
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
@@ -785,7 +785,7 @@ __device__ __forceinline__ void conv_epilogue(const DykConvDesc& desc, f32x4_t (
             const bool full = m0 + BM <= a.Cout && t_out[BN - 1] >= 0;
 #ifndef DYK_X_NOSLICED
             if constexpr (SLICED_OK) {
-                if (full && !((a.tune >> 21) & 1)) {
+                if (full && !conv_tune_abl_nofold(a.tune)) {
                     const bool chain = (flags & DYK_EPI_ADDEND) != 0;
 #ifdef DYK_X_ONLY1
                     sliced_bnbwd(integral_constant<int, DYK_ACT_MISH>{}, false_type{}); return;
@@ -992,7 +992,7 @@ void conv_igemm_kernel(const ConvArgs args) {
     const int tid_all = threadIdx.x;               // tables are built by the first 256 threads
     const int tid = tid_all & 255, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WN, wn = wid % WN;
-    if ((a.tune >> 18) & 1) return;            // ablation: empty kernel
+    if (conv_tune_abl_empty(a.tune)) return;            // ablation: empty kernel
 
     // Consecutive remapped ids share an XCD (and its 4 MB L2).  Pixel tiles vary fastest so that an XCD sees few
     // channel tiles: one 128-row slab of 3x3 weights is 9 x heavier than one 128-pixel slab of activations, and
@@ -1050,7 +1050,7 @@ void conv_igemm_kernel(const ConvArgs args) {
         tap_w[q] = wt * a.Cout * a.Cin;
     }
     __syncthreads();
-    if ((a.tune >> 19) & 1) return;            // ablation: tables only
+    if (conv_tune_abl_tables(a.tune)) return;            // ablation: tables only
 
     f32x4_t acc[MI][NI];
 #pragma unroll
@@ -1061,8 +1061,8 @@ void conv_igemm_kernel(const ConvArgs args) {
     const T* __restrict__ xg = sgpr_ptr((const T*)a.x);
     const T* __restrict__ wg = sgpr_ptr((const T*)a.w);
     // bits 16.. of `tune` are ablation switches for kernel analysis (tools/gpu_probe.py ablate): never set by the plan
-    const bool abl_nostore = (a.tune >> 16) & 1, abl_noloop = (a.tune >> 17) & 1;
-    const bool abl_nobar = (a.tune >> 22) & 1;      // analysis: K loop without its workgroup barrier (WRONG results: timing only)
+    const bool abl_nostore = conv_tune_abl_nostore(a.tune), abl_noloop = conv_tune_abl_noloop(a.tune);
+    const bool abl_nobar = conv_tune_abl_nobar(a.tune);     // analysis: K loop without its workgroup barrier (WRONG results: timing only)
     // K-groups split the input-channel chunks; the step count of group 0 (the larger half) drives the common barriers
     const int nchunks_all = a.Cin / BK;
     // this workgroup's share of the input-channel chunks (split-K slice), then the K-groups' halves of it
@@ -1564,11 +1564,9 @@ int dispatch_conv_halo(const DykConvDesc* d, hipStream_t stream) {
     if (!conv_halo_eligible(d, TH)) return DYK_ERR_UNSUPPORTED;
     const int row_bytes = d->Cin * (int)sizeof(T);
     if (row_bytes % 64) return DYK_ERR_ARG;
-    const bool k128 = (d->tune & 0xff) == 128 && row_bytes % 128 == 0;
-    int bm = d->Cout > 64 ? 128 : 64;
-    const int bm_code = (d->tune >> 24) & 0xf;
-    if (bm_code == 2) bm = 64;
-    if (bm_code == 3) bm = 128;
+    const bool k128 = conv_tune_kstep(d->tune) == 128 && row_bytes % 128 == 0;
+    const ConvRoute r = conv_route(d);
+    const int bm = conv_generic_tile(d, r, true).bm, bm_code = conv_chan_code(d, r);
     if constexpr (TH == 8) {
         // 32-channel tiles (8 x 20 patches only: a wave needs 16 channel rows): the data gradients into 32-channel tensors
         // at 256 x 320 (3x3 32 -> 64 of the first CSP block) spend a 64-row tile half on zero rows
@@ -1625,7 +1623,7 @@ int launch_conv_impl(const DykConvDesc* d, hipStream_t stream) {
 template <typename T, int BM, int BN, int BKB, int EPIK = 0>
 int launch_conv(const DykConvDesc* d, hipStream_t stream) {
     // 2-stage ring by default: 2-4 resident workgroups per CU beat a deeper ring unless the autotuner says otherwise
-    switch ((d->tune >> 8) & 0xf) {
+    switch (conv_tune_stages(d->tune)) {
     case 3: return launch_conv_impl<T, BM, BN, BKB, 3, 1, EPIK>(d, stream);
     case 4: return launch_conv_impl<T, BM, BN, BKB, 4, 1, EPIK>(d, stream);
     case 6: if constexpr ((size_t)6 * (BM + BN) * BKB + table_bytes<BN>() <= 160 * 1024) return launch_conv_impl<T, BM, BN, BKB, 6, 1, EPIK>(d, stream);
@@ -1634,20 +1632,16 @@ int launch_conv(const DykConvDesc* d, hipStream_t stream) {
     }
 }
 
-// tune word: bits 0..7 K-step bytes (64 | 128), 8..11 ring stages (2 | 3 | 4 | 6), 12..15 pixel tile (0 = 128, 1 = 80, 2 = 160),
-// 24..27 channel tile (0 = by Cout, 1 = 32, 2 = 64, 3 = 128); bits 16..23 are analysis switches
+// generic BN-pixel tile of the tune word (conv_tune.h): the family itself or the fallback of another one
 template <typename T, int BN, int EPIK = 0>
 int dispatch_conv_bn(const DykConvDesc* d, hipStream_t stream) {
     const int row_bytes = d->Cin * (int)sizeof(T);
     if ((row_bytes % 64) != 0) return DYK_ERR_ARG;
     // default K step: 128 bytes for long loops over wide inputs, else 64 (more resident workgroups); see DESIGN.md
     bool k128 = (row_bytes % 128) == 0 && (row_bytes / 128) * d->ntaps > 4 && d->Cin >= 512;
-    if ((d->tune & 0xff) == 64) k128 = false;
-    if ((d->tune & 0xff) == 128 && (row_bytes % 128) == 0) k128 = true;
-    int bm = d->Cout > 64 ? 128 : (d->Cout > 32 ? 64 : 32);
-    const int bm_code = (d->tune >> 24) & 0xf;
-    if (bm_code >= 1 && bm_code <= 3) bm = 16 << bm_code;
-    if constexpr (BN == 80) { if (bm == 32) bm = 64; }          // a wave needs 16 channel rows
+    if (conv_tune_kstep(d->tune) == 64) k128 = false;
+    if (conv_tune_kstep(d->tune) == 128 && (row_bytes % 128) == 0) k128 = true;
+    const int bm = conv_generic_tile(d, conv_route(d), false).bm;
     if (k128) {
         if (bm == 128) return launch_conv<T, 128, BN, 128, EPIK>(d, stream);
         if (bm == 64) return launch_conv<T, 64, BN, 128, EPIK>(d, stream);
@@ -1656,6 +1650,15 @@ int dispatch_conv_bn(const DykConvDesc* d, hipStream_t stream) {
     if (bm == 128) return launch_conv<T, 128, BN, 64, EPIK>(d, stream);
     if (bm == 64) return launch_conv<T, 64, BN, 64, EPIK>(d, stream);
     if constexpr (BN != 80) return launch_conv<T, 32, BN, 64, EPIK>(d, stream);
+    return DYK_ERR_UNSUPPORTED;
+}
+
+// K-grouped form (template parameter KG): 128-byte K step, 2-stage rings, 80 / 160 pixel tiles of at least 64 channel rows
+template <typename T, int EPIK = 0>
+int dispatch_conv_kg(const DykConvDesc* d, hipStream_t s) {
+    const ConvTile t = conv_generic_tile(d, conv_route(d), true);
+    if (conv_tile_code(d) == CONV_N80) return t.bm == 128 ? launch_conv_impl<T, 128, 80, 128, 2, 2, EPIK>(d, s) : launch_conv_impl<T, 64, 80, 128, 2, 2, EPIK>(d, s);
+    if (conv_tile_code(d) == CONV_N160) return t.bm == 128 ? launch_conv_impl<T, 128, 160, 128, 2, 2, EPIK>(d, s) : launch_conv_impl<T, 64, 160, 128, 2, 2, EPIK>(d, s);
     return DYK_ERR_UNSUPPORTED;
 }
 

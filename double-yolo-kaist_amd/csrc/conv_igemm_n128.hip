@@ -2,10 +2,6 @@
 // type and epilogue family so that make -j builds them in parallel).
 #include "conv_igemm_kernel.h"
 
-int dyk_conv_launch_n128b(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n128f(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n128n(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n128h(const DykConvDesc* d, hipStream_t s);
 int dyk_conv_launch_n128(const DykConvDesc* d, hipStream_t s) {
     if (d->dtype == DYK_F16) return dyk_conv_launch_n128h(d, s);
     if (d->flags & DYK_EPI_BNFWD) return dyk_conv_launch_n128n(d, s);

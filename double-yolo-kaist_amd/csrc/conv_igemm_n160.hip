@@ -2,9 +2,6 @@
 // epilogue family so that make -j builds them in parallel).
 #include "conv_igemm_kernel.h"
 
-int dyk_conv_launch_n160b(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n160n(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n160h(const DykConvDesc* d, hipStream_t s);
 int dyk_conv_launch_n160(const DykConvDesc* d, hipStream_t s) {
     if (d->dtype == DYK_F16) return dyk_conv_launch_n160h(d, s);
     if (d->flags & DYK_EPI_BNFWD) return dyk_conv_launch_n160n(d, s);

@@ -2,9 +2,6 @@
 // epilogue family so that make -j builds them in parallel).
 #include "conv_igemm_kernel.h"
 
-int dyk_conv_launch_n80b(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n80n(const DykConvDesc* d, hipStream_t s);
-int dyk_conv_launch_n80h(const DykConvDesc* d, hipStream_t s);
 int dyk_conv_launch_n80(const DykConvDesc* d, hipStream_t s) {
     if (d->dtype == DYK_F16) return dyk_conv_launch_n80h(d, s);
     if (d->flags & DYK_EPI_BNFWD) return dyk_conv_launch_n80n(d, s);

@@ -152,7 +152,7 @@ void conv_lt_kernel(const ConvArgs args, const int TH, const int TW) {
     const int per = (nchunks + KG - 1) / KG;
     const int c_begin = k_lo + (grp * per < nchunks ? grp * per : nchunks);
     const int c_end = c_begin + per < k_lo + nchunks ? c_begin + per : k_lo + nchunks;
-    const int nch = ((a.tune >> 17) & 1) ? 0 : c_end - c_begin;      // chunks of this group (tune bit 17, analysis: no K loop)
+    const int nch = conv_tune_abl_noloop(a.tune) ? 0 : c_end - c_begin;      // chunks of this group (tune bit 17, analysis: no K loop)
     const int frow = lane & 15, fslot = lane >> 4;
 
     // fragment addressing: weight rows are wave-constant (stage base + immediate), halo rows move with the tap
@@ -260,7 +260,7 @@ void conv_lt_kernel(const ConvArgs args, const int TH, const int TW) {
         wr = wr + 1 == LT_NA ? 0 : wr + 1;
         rd = rd + 1 == LT_NA ? 0 : rd + 1;
     };
-    for (int c = 0; c < (((a.tune >> 17) & 1) ? 0 : per); ++c) {
+    for (int c = 0; c < (conv_tune_abl_noloop(a.tune) ? 0 : per); ++c) {
         if (c < nch) {
             step(c, std::integral_constant<int, 0>{}); step(c, std::integral_constant<int, 1>{}); step(c, std::integral_constant<int, 2>{});
             step(c, std::integral_constant<int, 3>{}); step(c, std::integral_constant<int, 4>{}); step(c, std::integral_constant<int, 5>{});
@@ -345,7 +345,7 @@ int launch_conv_lt(const DykConvDesc* d, hipStream_t stream) {
     const int sk = conv_splitk_of(d);
     if ((d->Cin / 32) < KG * sk) return DYK_ERR_UNSUPPORTED;
     LtGeom g;
-    if (!lt_pick_patch(d->Hi, d->Wi, BN, GW, (d->tune >> 24) & 0xf, g)) return DYK_ERR_UNSUPPORTED;
+    if (!lt_pick_patch(d->Hi, d->Wi, BN, GW, conv_tune_lt_patch(d->tune), g)) return DYK_ERR_UNSUPPORTED;
     const size_t ring = (size_t)lt_rings_off<BM, BN>() + (size_t)KG * (LT_NA * (size_t)BM * LT_ROWB + 2 * (size_t)g.NB * 1024);
     size_t stage_c = lt_table_bytes<BM, BN>() + (size_t)BN * (BM * 2 + 16);
     if constexpr (EPIK == 1) {
@@ -371,11 +371,10 @@ int launch_conv_lt(const DykConvDesc* d, hipStream_t stream) {
     return DYK_OK;
 }
 
-// tune word of the large-tile kernels: pixel-tile code 5 (bits 12..15), shape in bits 8..11 (1 = 128 x 320, 2 = 256 x 160,
-// 3 = 128 x 160 with two K-groups), patch width code in bits 24..27 (0 = fewest halo rows, k: TW = 10 << k)
+// pixel-tile code 5 of the tune word (conv_tune.h): the shape picks the instantiation
 template <int EPIK, typename T = bf16_t>
 int dispatch_conv_lt(const DykConvDesc* d, hipStream_t stream) {
-    switch ((d->tune >> 8) & 0xf) {
+    switch (conv_tune_lt_shape(d->tune)) {
     case 1: return launch_conv_lt<2, 4, 1, EPIK, T>(d, stream);
     case 2: return launch_conv_lt<4, 2, 1, EPIK, T>(d, stream);
     case 3: return launch_conv_lt<2, 2, 2, EPIK, T>(d, stream);

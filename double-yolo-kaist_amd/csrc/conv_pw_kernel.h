@@ -372,7 +372,7 @@ int launch_conv_pw(const DykConvDesc* d, hipStream_t stream) {
     const int ntiles = dyk_div_up(Ntot, BN);
     const int mt = dyk_div_up(d->Cout, BM);
     if ((size_t)kc * BM * BKB > 64 * 1024) return DYK_ERR_UNSUPPORTED;            // resident weights of one channel tile
-    int nxs = (d->tune >> 8) & 0xf;
+    int nxs = conv_tune_pw_nxs(d->tune);
     if (nxs < 2) nxs = 3;
     if (nxs > 4) nxs = 4;
     const int ndxw = kc * C::IPCX / 4;
@@ -407,11 +407,10 @@ int launch_conv_pw(const DykConvDesc* d, hipStream_t stream) {
     return DYK_OK;
 }
 
-// tune word of the pointwise kernels: pixel-tile code 7 (bits 12..15), ring stages in bits 8..11 (0 = 3), bit 24 = 128-pixel tiles
-// (channel tiles <= 64 rows only), bit 25 = 32-pixel tiles (128-row channel tiles only)
+// pixel-tile code 7 of the tune word (conv_tune.h): bn128 for channel tiles <= 64 rows only, bn32 for 128-row channel tiles only
 template <int EPI, int ACTB, typename T = bf16_t>
 int dispatch_conv_pw(const DykConvDesc* d, hipStream_t s) {
-    const bool bn128 = (d->tune >> 24) & 1;
+    const bool bn128 = conv_tune_pw_bn128(d->tune);
     const bool k128 = (d->Cin % 64) == 0;
     if (d->Cout <= 32) {
         if (bn128) return k128 ? launch_conv_pw<32, 1, 128, 128, EPI, ACTB, T>(d, s) : launch_conv_pw<32, 1, 128, 64, EPI, ACTB, T>(d, s);
@@ -422,7 +421,7 @@ int dispatch_conv_pw(const DykConvDesc* d, hipStream_t s) {
         return k128 ? launch_conv_pw<64, 1, 64, 128, EPI, ACTB, T>(d, s) : launch_conv_pw<64, 1, 64, 64, EPI, ACTB, T>(d, s);
     }
     if (bn128) return DYK_ERR_UNSUPPORTED;
-    if ((d->tune >> 25) & 1)               // 32-pixel tiles: smaller ring stages and staging, two workgroups per CU at K = 128
+    if (conv_tune_pw_bn32(d->tune))             // 32-pixel tiles: smaller ring stages and staging, two workgroups per CU at K = 128
         return k128 ? launch_conv_pw<128, 2, 32, 128, EPI, ACTB, T>(d, s) : DYK_ERR_UNSUPPORTED;
     // 128-row channel tiles (two for 136..256 output channels: the activation tile is then read by two workgroups, through L2);
     // 32-pixel tiles where K = 256 and the epilogue operands of the BatchNorm-backward forms do not fit beside 64-pixel tiles

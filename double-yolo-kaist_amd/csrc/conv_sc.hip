@@ -21,7 +21,7 @@
 #include <stddef.h>
 #include <string.h>
 #include <type_traits>
-#include "dyk_common.h"
+#include "conv_tune.h"
 
 namespace {
 

@@ -246,6 +246,7 @@ SIGNATURES = {
     "dyk_conv_bnfwd_max_grid": (_i32, []),
     "dyk_conv_grid": (_i32, [_P(DykConvDesc)]),
     "dyk_conv_splitk_ws_bytes": (_i64, [_P(DykConvDesc), _P(_i32)]),
+    "dyk_conv_route": (_i32, [_P(DykConvDesc), _P(_i32)]),
     "dyk_conv_wgrad": (_i32, [_P(DykWgradDesc), _vp]),
     "dyk_conv_wgrad_splits": (_i32, [_P(DykWgradDesc)]),
     "dyk_conv_wgrad_variant": (_i32, [_P(DykWgradDesc)]),

@@ -1997,27 +1997,47 @@ def pw_eligible(d):
     return d.Cin % 32 == 0 and d.Cin <= 256 and d.Cout % 8 == 0 and d.ldx % 8 == 0 and d.ldy % 8 == 0
 
 
+# DykConvDesc.tune (decoded in csrc/conv_tune.h, which also says which fields alias per pixel-tile code; the layout is persisted
+# in bench_tuning.json and in tune caches): K-step bytes in the low byte | ring stages << 8 (tile 5: shape, tile 7: ring stages) |
+# pixel-tile code << 12 | channel-tile code << 24 (0 = by Cout, 1 = 32, 2 = 64 rows; tile 7: CONV_PW_BN128 / CONV_PW_BN32) | CONV_KG
+CONV_TILE_N128, CONV_TILE_N80, CONV_TILE_N160 = 0 << 12, 1 << 12, 2 << 12      # generic 128- / 80- / 160-pixel tiles
+CONV_TILE_HALO4, CONV_TILE_HALO8 = 3 << 12, 4 << 12      # 3x3 halo kernel, 4x20 / 8x20 pixel patches
+CONV_TILE_LT = 5 << 12             # large-tile 3x3 kernels (csrc/conv_lt_kernel.h)
+CONV_TILE_SC = 6 << 12             # resident-weight 3x3 data gradient (csrc/conv_sc.hip)
+CONV_TILE_PW = 7 << 12             # persistent pointwise kernels (csrc/conv_pw_kernel.h)
+CONV_PW_BN128, CONV_PW_BN32 = 1 << 24, 1 << 25
+CONV_KG = 1 << 28                  # K-grouped workgroups (two 4-wave groups over the two halves of Cin)
+
+
+def conv_tile(tune):
+    """the pixel-tile code of a conv tune word, as one of the CONV_TILE_* names"""
+    return tune & (0xf << 12)
+
+
+def _conv_word(bkb, stages, tile, bm=0):
+    return bkb | (stages << 8) | tile | (bm << 24)
+
+
 def _conv_candidates(d):
-    """tile configurations of dyk_conv_igemm for one problem: K-step bytes | ring stages << 8 | pixel tile << 12
-    (0 = 128, 1 = 80, 2 = 160 pixels, 3 / 4 = halo kernel 4x20 / 8x20; 16-bit types only) | channel tile << 24 (0 = by Cout, 2 = 64, 1 = 32)
-    | 1 << 28 = K-grouped workgroups"""
+    """tile configurations of dyk_conv_igemm for one problem (16-bit types: every generic tile, the halo kernel and the special
+    families where they apply; fp32: the 128-pixel tile)"""
     es = 2 if d.dtype in _H16 else 4
     bkbs = [64] + ([128] if (d.Cin * es) % 128 == 0 else [])
-    tiles = [0, 1, 2] if d.dtype in _H16 else [0]
+    tiles = [CONV_TILE_N128, CONV_TILE_N80, CONV_TILE_N160] if d.dtype in _H16 else [CONV_TILE_N128]
     if (d.dtype in _H16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi
             and d.Wi % 20 == 0 and d.Hi % 4 == 0):
-        tiles += [3] + ([4] if d.Hi % 8 == 0 else [])       # 3x3 halo kernel, 4x20 / 8x20 pixel patches
+        tiles += [CONV_TILE_HALO4] + ([CONV_TILE_HALO8] if d.Hi % 8 == 0 else [])
     bms = [0] + ([2] if d.Cout > 64 else ([1] if d.Cout > 32 else []))
     out = []
     for bkb in bkbs:
         for pipe in (2, 3, 4, 6):
             for t in tiles:
                 for bm in bms:
-                    if t in (1, 3, 4) and bm == 1:
+                    if t in (CONV_TILE_N80, CONV_TILE_HALO4, CONV_TILE_HALO8) and bm == 1:
                         continue                      # 80-pixel / halo tiles need >= 64 channel rows
-                    if t in (3, 4) and pipe != 2:
+                    if t in (CONV_TILE_HALO4, CONV_TILE_HALO8) and pipe != 2:
                         continue                      # the halo kernel has a fixed pipeline
-                    out.append(bkb | (pipe << 8) | (t << 12) | (bm << 24))
+                    out.append(_conv_word(bkb, pipe, t, bm))
     if (d.dtype in _H16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi and d.ncls <= 1
             and d.Cin % 32 == 0 and d.Wi % 20 == 0 and not (d.flags & (L.EPI_OUT_F32 | L.EPI_BNFWD))
             and os.environ.get("DYK_CONV_LT", "1") != "0"):
@@ -2027,27 +2047,24 @@ def _conv_candidates(d):
         for shape in (1, 2, 3):
             if shape == 2 and d.Cout < 256:
                 continue
-            out.append((5 << 12) | (shape << 8))
+            out.append(_conv_word(0, shape, CONV_TILE_LT))
     if (d.dtype == L.DYK_BF16 and d.ntaps == 9 and d.Cout == 32 and d.Cin == 64 and d.flags == L.EPI_BNBWD and d.isy == 1
             and d.Hg % 8 == 0 and d.Wg % 16 == 0 and os.environ.get("DYK_CONV_SC", "1") != "0"):
         # resident-weight 3x3 data gradient into 32-channel tensors (csrc/conv_sc.hip): one patch per tile for every tap and
         # parity class, epilogue from the accumulators; the front end falls back to the generic tile where it does not apply
-        out.append(6 << 12)
+        out.append(CONV_TILE_SC)
     if pw_eligible(d) and os.environ.get("DYK_CONV_PW", "1") != "0":
         # persistent resident-weight pointwise kernels (csrc/conv_pw_kernel.h): ring stages 2 | 3 | 4, 64- or (channel tiles <= 64
         # rows) 128-pixel tiles; the front end falls back to the generic 128-pixel tile where a shape does not fit
         for nxs in (2, 3, 4):
-            out.append((7 << 12) | (nxs << 8))
-            if d.Cout <= 64:
-                out.append((7 << 12) | (nxs << 8) | (1 << 24))
-            else:
-                out.append((7 << 12) | (nxs << 8) | (1 << 25))
+            out.append(_conv_word(0, nxs, CONV_TILE_PW))
+            out.append(_conv_word(0, nxs, CONV_TILE_PW) | (CONV_PW_BN128 if d.Cout <= 64 else CONV_PW_BN32))
     if d.dtype in _H16 and (d.Cin * es) % 128 == 0 and d.Cin >= 128 and os.environ.get("DYK_CONV_KG", "1") != "0":
         # K-grouped workgroups (two 4-wave groups over the two halves of Cin): for tiles that leave a CU one workgroup
-        for t in (1, 2):
+        for t in (CONV_TILE_N80, CONV_TILE_N160):
             for bm in bms:
                 if bm != 1:
-                    out.append(128 | (2 << 8) | (t << 12) | (bm << 24) | (1 << 28))
+                    out.append(_conv_word(128, 2, t, bm) | CONV_KG)
     return out
 
 
@@ -2072,20 +2089,20 @@ def _conv_split_candidates(d):
     if (d.Cin * es) % 64:
         return []
     bkbs = [128] if (d.Cin * es) % 128 == 0 else [64]
-    tiles_px = [(2, 160), (0, 128), (1, 80)] if d.dtype in _H16 else [(0, 128)]
+    tiles_px = [(CONV_TILE_N160, 160), (CONV_TILE_N128, 128), (CONV_TILE_N80, 80)] if d.dtype in _H16 else [(CONV_TILE_N128, 128)]
     bms = [(0, 128 if d.Cout > 64 else (64 if d.Cout > 32 else 32))] + ([(2, 64)] if d.Cout > 64 else [])
     for bkb in bkbs:
         kch = (d.Cin * es) // bkb
         for t, bn in tiles_px:
             for bmc, bm in bms:
-                if t == 1 and bm < 64:
+                if t == CONV_TILE_N80 and bm < 64:
                     continue
                 tiles = -(-npix // bn) * -(-d.Cout // bm)
                 for s in splits(tiles, kch):
                     for pipe in (2, 3):
-                        out.append((bkb | (pipe << 8) | (t << 12) | (bmc << 24), s))
-                    if d.dtype in _H16 and bkb == 128 and t in (1, 2) and bm >= 64 and kch // s >= 4 and os.environ.get("DYK_CONV_KG", "1") != "0":
-                        out.append((128 | (2 << 8) | (t << 12) | (bmc << 24) | (1 << 28), s))
+                        out.append((_conv_word(bkb, pipe, t, bmc), s))
+                    if d.dtype in _H16 and bkb == 128 and t in (CONV_TILE_N80, CONV_TILE_N160) and bm >= 64 and kch // s >= 4 and os.environ.get("DYK_CONV_KG", "1") != "0":
+                        out.append((_conv_word(128, 2, t, bmc) | CONV_KG, s))
     if (d.dtype in _H16 and d.ntaps == 9 and d.isy == 1 and d.osy == 1 and d.Hg == d.Hi and d.Wg == d.Wi
             and d.Cin % 32 == 0 and d.Wi % 20 == 0 and not (d.flags & L.EPI_OUT_F32) and os.environ.get("DYK_CONV_LT", "1") != "0"):
         for shape, (bm, bn, kg) in ((1, (128, 320, 1)), (2, (256, 160, 1)), (3, (128, 160, 2))):
@@ -2095,7 +2112,7 @@ def _conv_split_candidates(d):
                 continue
             tiles = (npix // bn) * -(-d.Cout // bm)
             for s in splits(tiles, (d.Cin // 32) // kg):
-                out.append(((5 << 12) | (shape << 8), s))
+                out.append((_conv_word(0, shape, CONV_TILE_LT), s))
     return out
 
 
@@ -2213,7 +2230,7 @@ def autotune(plan, cache=None):
                         # one-launch conv + BatchNorm: generic tiles whose launch fits the residency contract (the front end refuses the others)
                         keep = []
                         for c in cands:
-                            if (c >> 28) & 7 or ((c >> 12) & 0xf) in (3, 4):
+                            if c & CONV_KG or conv_tile(c) in (CONV_TILE_HALO4, CONV_TILE_HALO8):
                                 continue
                             d.tune = c
                             if lib.dyk_conv_grid(ctypes.byref(d)) <= BNFWD_MAX_GRID and fn(ctypes.byref(d), stream) == 0:

@@ -16,7 +16,7 @@ import ctypes
 import heapq
 
 from . import lib as L
-from .plan import wgrad_variant
+from .plan import CONV_TILE_PW, CONV_TILE_SC, conv_tile, wgrad_variant
 
 _IMG = ("image",)
 
@@ -105,9 +105,9 @@ def pair_signature(op, d, plan):
             return None                     # a one-launch conv + BatchNorm waits on its own workgroups: single problem only
         if d.splitk > 1:
             return None                     # split-K across workgroups (private slabs and tile counters): single problem only
-        if ((d.tune >> 12) & 0xf) == 7:
+        if conv_tile(d.tune) == CONV_TILE_PW:
             return None                     # persistent pointwise kernels (csrc/conv_pw_kernel.h): single problem only
-        if ((d.tune >> 12) & 0xf) == 6:
+        if conv_tile(d.tune) == CONV_TILE_SC:
             return None                     # resident-weight data gradient (csrc/conv_sc.hip): single problem only -- as one half of a
                                             # two-problem launch it would fall back to the generic kernel, whose epilogue rounds differently
         return (op, _bytes(d, L.DykConvDesc, "dtype", "twin"), _nulls(d, ("scale", "shift", "res", "stats", "aux0", "aux1", "add")))

@@ -162,9 +162,11 @@ typedef struct DykConvDesc {
     int32_t tune;                   /* 0 = built-in heuristic; else tile configuration chosen by the plan compiler's
                                        per-shape measurement: bits 0..7 K-step bytes (64|128), 8..11 LDS ring stages
                                        (2|3|4|6), 12..15 pixel tile (0 = 128, 1 = 80, 2 = 160, 3 / 4 = halo kernel, 5 = large-tile kernels,
-                                       6 = resident-weight 3x3 data gradient into 32-channel tensors; bf16), 24..27 channel
-                                       tile (0 = by Cout, 1 = 32, 2 = 64, 3 = 128); bits 16..23 analysis switches; 1 << 28 = two K-groups per
-                                       workgroup (512 threads, halves of Cin, bf16 / 128-byte K step / 80|160-pixel tiles) */
+                                       6 = resident-weight 3x3 data gradient into 32-channel tensors; bf16, 7 = pointwise kernels),
+                                       24..27 channel tile (0 = by Cout, 1 = 32, 2 = 64, 3 = 128); bits 16..23 analysis switches;
+                                       1 << 28 = two K-groups per workgroup (512 threads, halves of Cin, 128-byte K step /
+                                       80|160-pixel tiles).  Summary only: bits 8..11 and 24..27 mean other things under tiles 5
+                                       and 7 -- the layout, field by field, is the comment at the top of csrc/conv_tune.h */
     const struct DykConvDesc* twin; /* HOST pointer or NULL.  Two-problem launch: a second problem of IDENTICAL geometry, flags and
                                        tile configuration (every non-pointer field equal) whose pointer fields x, w, y, scale,
                                        shift, res, stats, aux0, aux1, add are used -- one launch covers both, the workgroups of
@@ -196,6 +198,11 @@ int dyk_conv_grid(const DykConvDesc* desc);
 /* split-K scratch of `desc` (its tune word and splitk): bytes of sk_ws, and (via *tiles, may be NULL) the words of sk_cnt;
  * upper bounds that hold for every kernel the tune word can select.  0 when splitk <= 1; negative error code on bad input */
 int64_t dyk_conv_splitk_ws_bytes(const DykConvDesc* desc, int32_t* tiles);
+/* host-only: the kernel family dyk_conv_igemm tries first for `desc` (its tune word, dtype, flags) -- the pixel-tile codes of
+ * DykConvDesc.tune, 0 / 1 / 2 = generic 128- / 80- / 160-pixel tiles, 3 / 4 halo, 5 large-tile, 6 resident-weight data gradient,
+ * 7 pointwise; 8 = K-grouped -- and (via *fallback_tile, may be NULL) the generic tile code that takes the problem when the
+ * family refuses it, -1 = none.  Negative: error code (a word no kernel runs).  Layout and aliasing: csrc/conv_tune.h */
+int dyk_conv_route(const DykConvDesc* desc, int32_t* fallback_tile);
 
 /* ------------------------------------------------------------------------------------
  * Convolution weight gradient (split-K MFMA GEMM over output pixels, fp32 atomics):

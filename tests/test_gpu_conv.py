@@ -1367,3 +1367,50 @@ def test_pointwise_conv_kernels(case):
                     assert torch.allclose(st[0], r1, rtol=2e-3, atol=5e-2 * n ** 0.5), (hex(tune), flags, actname)
                     assert torch.allclose(st[1], r2, rtol=2e-3, atol=5e-2 * n ** 0.5), (hex(tune), flags, actname)
     assert ran_b >= 9, ran_b
+
+
+# (k, Cin, family, fallback tile) of the problems below, in the order of make_conv_queries.REFUSED_WORDS: B = 1, Cout = 64, 9 x 13 map
+REFUSED_CASES = [
+    (3, 64, 3, 1),      # halo 4x20: the width is not a multiple of 20
+    (3, 64, 4, 2),      # halo 8x20
+    (3, 64, 5, 2),      # large tile: no patch fits the map
+    (1, 288, 7, 0),     # pointwise: K > 256; bit 25 of its word reads as channel code 2 on the generic tile
+    (1, 32, 8, 2),      # K-grouped: the row is shorter than 128 bytes
+    (3, 64, 6, 0),      # resident-weight data gradient: a forward convolution
+]
+
+
+def test_refused_family_runs_its_generic_tile():
+    """a special kernel family that refuses a problem hands it to the generic tile dyk_conv_route names: the output equals, bit
+    for bit, the launch of the generic word with the same K step, stages and channel code; with bit 23 (no fallback) the same
+    word returns DYK_ERR_UNSUPPORTED and writes nothing"""
+    import ctypes
+    import sys
+    from dyk import lib as L, ops
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_conv_queries as Q
+    lib = L.load()
+    B, Cout, H, W = 1, 64, 9, 13
+    assert len(REFUSED_CASES) == len(Q.REFUSED_WORDS)
+    for (k, Cin, family, fallback), (special, generic) in zip(REFUSED_CASES, Q.REFUSED_WORDS):
+        g = torch.Generator().manual_seed(77)
+        x = torch.randn(B, Cin, H, W, generator=g).bfloat16().float()
+        w = (torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5).bfloat16().float()
+        y_ref = F.conv2d(x, w, padding=k // 2)
+        xd = ops.to_nhwc(x.cuda(), torch.bfloat16)
+        wp = ops.pack_weight(w.cuda(), torch.bfloat16)
+        out = torch.full((B, H, W, Cout), 7.0, dtype=torch.bfloat16, device="cuda")
+        d = ops.make_conv_desc(xd, wp, out, Hi=H, Wi=W, Cin=Cin, Cout=Cout, Hg=H, Wg=W, Ho=H, Wo=W, taps=ops.fwd_taps(k, k // 2))
+        d.tune = special
+        fb = ctypes.c_int32(-7)
+        assert (lib.dyk_conv_route(ctypes.byref(d), ctypes.byref(fb)), fb.value) == (family, fallback), hex(special)
+        assert (generic >> 12) & 0xf == fallback and generic >> 28 == 0, hex(generic)
+        d.tune = special | (1 << 23)
+        assert lib.dyk_conv_igemm(ctypes.byref(d), None) == -3, hex(special)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()), (hex(special), "a refused launch wrote to the output")
+        y_gen = ops.conv2d_fwd(xd, wp, k, 1, k // 2, Cout, tune=generic)
+        y_sp = ops.conv2d_fwd(xd, wp, k, 1, k // 2, Cout, tune=special)
+        assert torch.equal(y_sp, y_gen), (hex(special), hex(generic))
+        err = (ops.to_nchw(y_sp).cpu() - y_ref).abs().max().item()
+        assert err <= 1.2e-2 * max(1.0, y_ref.abs().max().item()), (hex(special), err)
