@@ -153,6 +153,52 @@ __global__ void yolo_decode_kernel(DykDecodeDesc d) {
     }
 }
 
+// Wide heads (na*no > 32), inference: the permute of head_permute_fwd_kernel and the decode above in one launch.  One thread per
+// element of p, in p's order [b][a][y][x][o]: consecutive threads take consecutive o, so the store to p, the store to io (rows
+// (a*ny + y)*nx + x of image b are p's cells in the same order) and the read of y (runs of `no` floats per cell) are
+// coalesced -- the kernel above gives a thread a whole cell and walks it at a stride of no*4 bytes.  Per channel the SAME
+// expressions as above, so the values are bit-identical to the two-launch sequence.  I: 32-bit indices where every extent fits.
+template <typename I>
+__global__ __launch_bounds__(256) void head_decode_kernel(DykHeadDecodeDesc d, I total) {
+    const I no = (I)d.no, nx = (I)d.nx, ny = (I)d.ny, na = (I)d.na;
+    for (I i = blockIdx.x * (I)blockDim.x + threadIdx.x; i < total; i += (I)gridDim.x * (I)blockDim.x) {
+        const int o = (int)(i % no);
+        I q = i / no;
+        const int x = (int)(q % nx); q /= nx;
+        const int y = (int)(q % ny); q /= ny;
+        const int a = (int)(q % na);
+        const I b = q / na;
+        const float t = d.y[((b * ny + (I)y) * nx + (I)x) * (I)d.ld + (I)(a * d.no + o)];
+        d.p[i] = t;
+        float v;
+        if (o >= 4) {
+            v = 1.f / (1.f + expf(-t));
+        } else if (d.v4) {
+            const float s = 1.f / (1.f + expf(-t));
+            if (o == 0) {
+                v = (s * 2.f - 0.5f + (float)x) * d.stride;
+            } else if (o == 1) {
+                v = (s * 2.f - 0.5f + (float)y) * d.stride;
+            } else {
+                const float an = d.anchor_vec[2 * a + (o - 2)];
+                const float w2 = s * 2.f;
+                v = (w2 * w2) * an * d.stride;
+            }
+        } else {
+            if (o == 0) {
+                v = (1.f / (1.f + expf(-t)) + (float)x) * d.stride;
+            } else if (o == 1) {
+                v = (1.f / (1.f + expf(-t)) + (float)y) * d.stride;
+            } else {
+                const float an = d.anchor_vec[2 * a + (o - 2)];
+                v = expf(t) * an * d.stride;
+            }
+        }
+        const I row = (I)d.row_offset + ((I)a * ny + (I)y) * nx + (I)x;
+        d.io[(b * (I)d.rows_total + row) * no + (I)o] = v;
+    }
+}
+
 inline int grid_for(long n, int per_block) {
     long g = (n + per_block - 1) / per_block;
     return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
@@ -231,6 +277,24 @@ extern "C" int dyk_yolo_decode(const DykDecodeDesc* d, void* stream) {
     return DYK_OK;
 }
 
+extern "C" int dyk_head_decode(const DykHeadDecodeDesc* d, void* stream) {
+    if (!d || !d->y || !d->p || !d->io || d->B <= 0 || d->na <= 0 || d->na > 8 || d->ny <= 0 || d->nx <= 0 || d->no < 5)
+        return DYK_ERR_ARG;
+    const long cells = (long)d->na * d->ny * d->nx;
+    if ((long)d->na * d->no > d->ld) return DYK_ERR_ARG;
+    if (d->row_offset < 0 || d->row_offset + cells > d->rows_total) return DYK_ERR_ARG;
+    const long total = (long)d->B * cells * d->no;
+    const long y_extent = (long)d->B * d->ny * d->nx * d->ld, io_extent = (long)d->B * d->rows_total * d->no;
+    const int grid = grid_for(total, 256);
+    // (the grid stride is at most 8192 * 256: an index below 2^31 cannot wrap a 32-bit counter)
+    if (total < (1L << 31) && y_extent < (1L << 31) && io_extent < (1L << 31))
+        hipLaunchKernelGGL(head_decode_kernel<uint32_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, (uint32_t)total);
+    else
+        hipLaunchKernelGGL(head_decode_kernel<long>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, total);
+    DYK_LAUNCH_CHECK();
+    return DYK_OK;
+}
+
 extern "C" int dyk_run_commands(const DykCommand* cmds, int32_t n, void* stream, int32_t* failed_index) {
     if (!cmds || n < 0) return DYK_ERR_ARG;
     // analysis (timing only, results are garbage): DYK_SKIP_OPS=<op code>,<op code>,... leaves those commands out of every
@@ -296,6 +360,7 @@ extern "C" int dyk_run_commands(const DykCommand* cmds, int32_t n, void* stream,
                     hipMemsetAsync(m->p[1], 0, (size_t)m->i[1], (hipStream_t)stream) != hipSuccess) rc = DYK_ERR_HIP;
                 break;
             case DYK_OP_YOLO_DECODE: rc = dyk_yolo_decode((const DykDecodeDesc*)dp, stream); break;
+            case DYK_OP_HEAD_DECODE: rc = dyk_head_decode((const DykHeadDecodeDesc*)dp, stream); break;
             case DYK_OP_DW_FWD: rc = dyk_dwconv_fwd((const DykDwDesc*)dp, stream); break;
             case DYK_OP_DW_DGRAD: rc = dyk_dwconv_dgrad((const DykDwDesc*)dp, stream); break;
             case DYK_OP_DW_WGRAD: rc = dyk_dwconv_wgrad((const DykDwDesc*)dp, stream); break;

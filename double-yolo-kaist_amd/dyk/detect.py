@@ -8,6 +8,9 @@ from . import lib as L
 from .lib import check, load
 
 
+NMS_MAX_CLASSES = 16       # entries of DykNmsDesc.classes (include/dyk_hip.h): the class filter of non_max_suppression
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -197,6 +200,10 @@ def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=T
     True / False override the environment."""
     if merge is None:
         merge = os.environ.get("DYK_NMS_MERGE", "0") not in ("", "0")
+    cl = list(classes) if classes else []
+    if len(cl) > NMS_MAX_CLASSES:
+        raise ValueError("non_max_suppression(classes=...) takes at most %d class indices (DykNmsDesc.classes), got %d"
+                         % (NMS_MAX_CLASSES, len(cl)))
     _require_cuda(prediction, "non_max_suppression")
     pred = prediction.detach().float().contiguous()
     B, N, no = pred.shape
@@ -213,9 +220,8 @@ def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=T
     d.B, d.N, d.no = B, N, no
     d.conf_thres, d.iou_thres = float(conf_thres), float(iou_thres)
     d.multi_label, d.agnostic, d.max_num = 1 if multi else 0, 1 if agnostic else 0, int(max_num)
-    cl = list(classes) if classes else []
     d.n_classes = len(cl)
-    for i, c in enumerate(cl[:16]):
+    for i, c in enumerate(cl):
         d.classes[i] = int(c)
     if merge:
         check(lib.dyk_nms_ex(ctypes.byref(d), L.NMS_MERGE, _stream()), "dyk_nms_ex")

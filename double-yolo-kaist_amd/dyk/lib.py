@@ -25,7 +25,7 @@ EMA_MAX_REGIONS = 4        # DYK_EMA_MAX_REGIONS (include/dyk_hip.h): regions of
  OP_UPSAMPLE_FWD, OP_UPSAMPLE_BWD, OP_MAXPOOL_FWD, OP_MAXPOOL_BWD, OP_SE_POOL, OP_SE_FC_FWD, OP_SE_FC_BWD,
  OP_SE_SCALE, OP_BN_BWD_PARAMS, OP_BN_FOLD, OP_WFUSE_WEIGHTS, OP_WFUSE_BWD_PARAMS, OP_HEAD_PERMUTE_FWD,
  OP_HEAD_PERMUTE_BWD, OP_PATCH_GATHER, OP_MEMSET, OP_YOLO_DECODE, OP_DW_FWD, OP_DW_DGRAD, OP_DW_WGRAD,
- OP_CAST_PAD_ROWS, OP_BN_FWD_FUSED, OP_GRAD_REDUCE, OP_STEM_FWD, OP_STEM_WGRAD) = range(1, 34)
+ OP_CAST_PAD_ROWS, OP_BN_FWD_FUSED, OP_GRAD_REDUCE, OP_STEM_FWD, OP_STEM_WGRAD, OP_HEAD_DECODE) = range(1, 35)
 
 
 class DykLibraryError(RuntimeError):
@@ -156,6 +156,12 @@ class DykSchedEntry(ctypes.Structure):
 class DykDecodeDesc(ctypes.Structure):
     _fields_ = [("p", _vp), ("io", _vp), ("B", _i32), ("na", _i32), ("ny", _i32), ("nx", _i32), ("no", _i32),
                 ("rows_total", _i32), ("row_offset", _i32), ("v4", _i32), ("stride", _f32),
+                ("anchor_vec", _f32 * 16)]
+
+
+class DykHeadDecodeDesc(ctypes.Structure):
+    _fields_ = [("y", _vp), ("p", _vp), ("io", _vp), ("B", _i32), ("na", _i32), ("ny", _i32), ("nx", _i32), ("no", _i32),
+                ("ld", _i32), ("rows_total", _i32), ("row_offset", _i32), ("v4", _i32), ("stride", _f32),
                 ("anchor_vec", _f32 * 16)]
 
 
@@ -297,6 +303,7 @@ SIGNATURES = {
     "dyk_schedule_graph_launch": (_i32, [_vp, _vp]),
     "dyk_schedule_graph_destroy": (_i32, [_vp]),
     "dyk_yolo_decode": (_i32, [_P(DykDecodeDesc), _vp]),
+    "dyk_head_decode": (_i32, [_P(DykHeadDecodeDesc), _vp]),
     "dyk_build_targets": (_i32, [_P(DykTargetsDesc), _vp]),
     "dyk_yolo_loss": (_i32, [_P(DykLossDesc), _P(DykTargetsDesc), _vp]),
     "dyk_nms_workspace_bytes": (_i64, [_i32, _i32, _i32]),

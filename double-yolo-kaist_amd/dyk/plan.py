@@ -22,7 +22,8 @@ from . import lib as L
 from .ops import conv_out_size, dgrad_classes, fwd_taps, maxpool_out_size
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
-HEAD_LD = 32            # head conv outputs / their gradients live in 32-channel rows
+HEAD_LD = 32            # head conv outputs / their gradients live in rows of a multiple of 32 channels (head_ld)
+HEAD_MAX_NA = 8         # anchors per head the decode kernels take (DykDecodeDesc.anchor_vec)
 FWD_SLOTS_CAP = 32    # most replicas of a forward statistics buffer.  32 = every layer's
 # finalize rides on its normalise launch (42 launches of 9 us fewer on the forward chain of the target cfg: -0.2 ms in an A/B
 # against 256 replicas, round 3; the 10 240 tiles of a 256 x 320 layer then put 320 fp64 atomics on an address -- the backward
@@ -48,6 +49,14 @@ STAT_SLOTS = 16   # replicas of every per-channel fp64 reduction buffer of the b
 
 def _ru(n, a):
     return (n + a - 1) // a * a
+
+
+def head_ld(channels):
+    """Row length (channels) of a detection head's conv output (fp32) and of its gradient (compute dtype), for
+    channels = na * (5 + nc): 32 up to 32 channels, the next multiple of 32 above.  32 channels are the K step of the bf16 MFMA
+    that consumes the head gradient (the data gradient reads K = the padded row, zero weight rows under the pad) and make fp32
+    rows whole 128-byte lines."""
+    return max(HEAD_LD, _ru(channels, HEAD_LD))
 
 
 class TRef:
@@ -707,14 +716,13 @@ class _Emitter:
         return z, rec
 
     def _epi_bias(self, rec, d, xfill, Ho, Wo, out_layer):
-        """no BatchNorm: bias epilogue; detection heads go to fp32 rows of HEAD_LD channels"""
+        """no BatchNorm: bias epilogue; detection heads go to fp32 rows of head_ld(cout) channels"""
         i, cout, act = rec["i"], rec["cout"], rec["act"]
         if rec["dw"]:
             raise NotImplementedError("depthwise conv without batch_normalize (layer %d)" % i)
         is_head = (i + 1 < len(self.defs) and self.defs[i + 1]["type"] == "yolo")
         if is_head:
-            assert cout <= HEAD_LD
-            z = self.new_act(self.B, Ho, Wo, cout, ld=HEAD_LD, esize=4)
+            z = self.new_act(self.B, Ho, Wo, cout, ld=head_ld(cout), esize=4)
             d.flags = L.EPI_AFFINE | L.EPI_OUT_F32
         else:
             z = self.alloc_out(out_layer, self.B, Ho, Wo, cout)
@@ -956,20 +964,30 @@ class _Emitter:
         return z, {"kind": "upsample", "i": i, "x": x_in, "z": z}
 
     def _fwd_yolo(self, i, m, mod, y_in):
-        B, plan = self.B, self.plan          # y_in: head conv output, fp32, ld = HEAD_LD
+        B, plan = self.B, self.plan          # y_in: head conv output, fp32, ld = head_ld(na * no)
         self.consume(y_in)
         na, no = mod.na, mod.no
+        if na > HEAD_MAX_NA:
+            raise NotImplementedError("[yolo] with %d anchors (layer %d): the decode kernels take at most %d per head"
+                                      % (na, i, HEAD_MAX_NA))
+        if y_in.C != na * no:
+            raise ValueError("[yolo] (layer %d) expects %d = %d * (5 + %d) channels from the [convolutional] in front of it, "
+                             "got filters=%d" % (i, na * no, na, no - 5, y_in.C))
         ny, nx = y_in.H, y_in.W
         p = torch.empty((B, na, ny, nx, no), dtype=torch.float32, device=self.device)
         head = len(plan.p_out)
         plan.p_out.append(p)
-        hd = self.misc()
-        hd.p[1] = p.data_ptr()
-        hd.i[0], hd.i[1], hd.i[2], hd.i[3], hd.i[4], hd.i[5] = B, ny, nx, na, no, y_in.ld
-        self.fill(hd, {0: y_in})
-        plan.fwd.append((L.OP_HEAD_PERMUTE_FWD, hd))
+        # inference, wide head (rows beyond HEAD_LD channels): permute and decode share one launch (_fwd_decode)
+        fused = not self.training and na * no > HEAD_LD
+        if not fused:
+            hd = self.misc()
+            hd.p[1] = p.data_ptr()
+            hd.i[0], hd.i[1], hd.i[2], hd.i[3], hd.i[4], hd.i[5] = B, ny, nx, na, no, y_in.ld
+            self.fill(hd, {0: y_in})
+            plan.fwd.append((L.OP_HEAD_PERMUTE_FWD, hd))
         self.yolo_rows.append(na * ny * nx)
         return y_in, {"kind": "yolo", "i": i, "y": y_in, "na": na, "no": no, "ny": ny, "nx": nx, "head": head, "p": p,
+                      "fused_decode": fused,
                       "stride": mod.stride, "anchor_vec": [float(v) for v in mod.anchor_vec.reshape(-1).tolist()]}
 
     def _fwd_dropout(self, i, m, mod, cur):
@@ -992,13 +1010,22 @@ class _Emitter:
         r0 = 0
         for j in model.yolo_layers:
             rec = self.info[j]
-            dd = self.keep(L.DykDecodeDesc())
+            if rec["fused_decode"]:
+                # wide head: y -> p and the decoded rows of io in one launch (the cell-per-thread decode walks a cell at a stride
+                # of no * 4 bytes and would re-read the p a launch before it has just written)
+                dd = self.keep(L.DykHeadDecodeDesc())
+                dd.ld = rec["y"].ld
+                self.fill(dd, y=rec["y"])
+                op = L.OP_HEAD_DECODE
+            else:
+                dd = self.keep(L.DykDecodeDesc())
+                op = L.OP_YOLO_DECODE
             dd.p, dd.io = rec["p"].data_ptr(), plan.io.data_ptr()
             dd.B, dd.na, dd.ny, dd.nx, dd.no = B, rec["na"], rec["ny"], rec["nx"], rec["no"]
             dd.rows_total, dd.row_offset, dd.v4, dd.stride = rows_total, r0, 1 if self.v4 else 0, float(rec["stride"])
             for q, v in enumerate(rec["anchor_vec"]):
                 dd.anchor_vec[q] = v
-            plan.fwd.append((L.OP_YOLO_DECODE, dd))
+            plan.fwd.append((op, dd))
             r0 += rec["na"] * rec["ny"] * rec["nx"]
 
     # ---------------------------------------------------------------- backward: BatchNorm + conv gradients
@@ -1249,10 +1276,10 @@ class _Emitter:
 
     def _bwd_yolo(self, i, rec):
         y_in = rec["y"]
-        gy = self.gref(y_in, ld=HEAD_LD)          # dtype rows of 32 channels, zero padded
+        gy = self.gref(y_in, ld=y_in.ld)          # dtype rows of head_ld channels, zero padded (the data gradient's K)
         hd = self.misc()
         hd.p[2] = self.store.g_ptr(self.info[i - 1]["bias_name"])
-        hd.i[0], hd.i[1], hd.i[2], hd.i[3], hd.i[4], hd.i[5], hd.i[6] = self.B, rec["ny"], rec["nx"], rec["na"], rec["no"], HEAD_LD, self.code
+        hd.i[0], hd.i[1], hd.i[2], hd.i[3], hd.i[4], hd.i[5], hd.i[6] = self.B, rec["ny"], rec["nx"], rec["na"], rec["no"], gy.ld, self.code
         self.fill(hd, {1: gy})
         self.plan.dyn_dp.append((hd, rec["head"]))
         self.plan.bwd.append((L.OP_HEAD_PERMUTE_BWD, hd))

@@ -257,7 +257,11 @@ def accesses(op, d, mem, plan):
     elif op == L.OP_YOLO_DECODE:
         rd(mem.interval(_v(d.p), d.B * d.na * d.ny * d.nx * d.no * 4))
         wr(mem.interval(_v(d.io), d.B * d.rows_total * d.no * 4))
-    else:                                   # MEMSET over a span of blocks, and anything not listed above
+    elif op == L.OP_HEAD_DECODE:
+        rd(T(d.y, d.ld, d.na * d.no, 4))
+        wr(mem.interval(_v(d.p), d.B * d.na * d.ny * d.nx * d.no * 4))
+        wr(mem.interval(_v(d.io), d.B * d.rows_total * d.no * 4))
+    else:                                  # MEMSET over a span of blocks, and anything not listed above
         return R, W, True
     return R, W, False
 
@@ -326,6 +330,8 @@ def estimate_cost_us(op, d, plan):
         return 50.0
     if op in (L.OP_STEM_FWD, L.OP_STEM_WGRAD):
         return 10.0 + float(d.B) * d.Ho * d.Wo * d.Cout * _es(d.dtype) / 3e6
+    if op == L.OP_HEAD_DECODE:              # y read once, p and the io rows written: three passes over B*na*ny*nx*no floats
+        return 4.0 + 3.0 * float(d.B) * d.na * d.ny * d.nx * d.no * 4 / 3e6
     return 5.0
 
 

@@ -626,6 +626,7 @@ enum {
     DYK_OP_GRAD_REDUCE = 31,    /* Misc: p0=G p1=part p2=table i0=n_entries i1=total_chunks -> dyk_grad_reduce */
     DYK_OP_STEM_FWD = 32,       /* DykStemDesc -> dyk_stem_conv_fwd */
     DYK_OP_STEM_WGRAD = 33,     /* DykStemDesc -> dyk_stem_conv_wgrad */
+    DYK_OP_HEAD_DECODE = 34,    /* DykHeadDecodeDesc -> dyk_head_decode */
     DYK_OP_COUNT_
 };
 
@@ -669,6 +670,25 @@ typedef struct DykDecodeDesc {
     float anchor_vec[2 * 8];        /* (w, h) per anchor, already divided by stride (models.py:182) */
 } DykDecodeDesc;
 int dyk_yolo_decode(const DykDecodeDesc* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * One-launch inference head for wide heads (na*no > 32): y [B,ny,nx,ld] fp32, the head conv's
+ * output (channel = a*no + o, ld >= na*no), is read once and leaves BOTH
+ *   p  [B,na,ny,nx,no] fp32   = what dyk_head_permute_fwd writes, and
+ *   io rows [row_offset + (a*ny + y)*nx + x] of [B, rows_total, no] = what dyk_yolo_decode writes
+ * from that p, bit for bit.  One thread per output element, consecutive threads on consecutive o.
+ * ---------------------------------------------------------------------------------- */
+typedef struct DykHeadDecodeDesc {
+    const float* y;
+    float* p;
+    float* io;
+    int32_t B, na, ny, nx, no, ld;
+    int32_t rows_total, row_offset;
+    int32_t v4;
+    float stride;
+    float anchor_vec[2 * 8];        /* as DykDecodeDesc.anchor_vec */
+} DykHeadDecodeDesc;
+int dyk_head_decode(const DykHeadDecodeDesc* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Target assignment and loss (build_utils/utils.py:209-384).
