@@ -227,6 +227,7 @@ def build_targets(p, targets, model):
 
 
 def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=True, classes=None, agnostic=False,
-                        max_num=100, merge=None):
+                        max_num=100, merge=None, candidates=None):
     from dyk import detect
-    return detect.non_max_suppression(prediction, conf_thres, iou_thres, multi_label, classes, agnostic, max_num, merge=merge)
+    return detect.non_max_suppression(prediction, conf_thres, iou_thres, multi_label, classes, agnostic, max_num, merge=merge,
+                                      candidates=candidates)

@@ -1,4 +1,5 @@
-"""Host side of the loss / target-assignment / NMS kernels (dyk_yolo_loss, dyk_build_targets, dyk_nms, dyk_nms_ex)."""
+"""Host side of the loss / target-assignment / NMS kernels (dyk_yolo_loss, dyk_build_targets, dyk_nms, dyk_nms_ex,
+dyk_nms_rows)."""
 import ctypes
 import os
 
@@ -190,44 +191,94 @@ def compute_loss(p, targets, model):
     return {"box_loss": lbox, "obj_loss": lobj, "class_loss": lcls}
 
 
+# Multi-label calls with at least this many classes take the row-wise route (dyk_nms_rows); below it, and in every
+# best-class call, the per-image route (dyk_nms / dyk_nms_ex).  Measured: profiles/nms_rows.json, DESIGN.md section 15.
+NMS_ROWS_MIN_NC = 2
+NMS_ROWS_MIN_CANDIDATES = 8192      # floor of the default candidate capacity: a small N does not overflow at once
+
+_nms_routes = {"image": 0, "rows": 0, "rows_overflow": 0}
+
+
+def nms_route_counts():
+    """calls of non_max_suppression per route since import: "image" = dyk_nms / dyk_nms_ex, "rows" = dyk_nms_rows,
+    "rows_overflow" = the row-wise calls that found an image with more candidates than the capacity and ran the batch again on
+    the "image" route (counted there too)."""
+    return dict(_nms_routes)
+
+
+def nms_default_candidates(N):
+    """candidates one image may hold on the row-wise route when `candidates` is None: what a best-class call holds, N, with a
+    floor"""
+    return max(int(N), NMS_ROWS_MIN_CANDIDATES)
+
+
 def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=True, classes=None, agnostic=False,
-                        max_num=100, return_rows=False, merge=None):
+                        max_num=100, return_rows=False, merge=None, candidates=None):
     """reference build_utils/utils.py:387-464 -> list (per image) of [n,6] tensors or None.
 
     merge: the reference's `merge` setting (utils.py:398, False as shipped; :450-454): every kept box becomes the
     score-weighted mean of all candidates that overlap it by more than iou_thres, in images with 1 < n < 3000 candidates.
     None reads DYK_NMS_MERGE from the environment (unset or 0 = off), so an unchanged evaluate.py can switch it on;
-    True / False override the environment."""
+    True / False override the environment.
+
+    candidates: multi-label calls (multi_label and more than one class) hold at most this many candidates per image in
+    their workspace (dyk_nms_rows); None = max(N, 8192).  An image with more makes the call run the batch again with the
+    workspace for N * nc candidates (dyk_nms / dyk_nms_ex), so the result never depends on it."""
     if merge is None:
         merge = os.environ.get("DYK_NMS_MERGE", "0") not in ("", "0")
     cl = list(classes) if classes else []
     if len(cl) > NMS_MAX_CLASSES:
         raise ValueError("non_max_suppression(classes=...) takes at most %d class indices (DykNmsDesc.classes), got %d"
                          % (NMS_MAX_CLASSES, len(cl)))
+    if candidates is not None and int(candidates) < 1:
+        raise ValueError("non_max_suppression(candidates=...) must be at least 1, got %r" % (candidates,))
     _require_cuda(prediction, "non_max_suppression")
     pred = prediction.detach().float().contiguous()
     B, N, no = pred.shape
     nc = no - 5
     multi = bool(multi_label) and nc > 1
     lib = load()
-    d = L.DykNmsDesc()
-    per = int(lib.dyk_nms_workspace_bytes(N, no, 1 if multi else 0))
-    ws = torch.empty(B * per, dtype=torch.uint8, device=pred.device)
-    out = torch.zeros((B, max_num, 6), dtype=torch.float32, device=pred.device)
-    rows = torch.zeros((B, max_num), dtype=torch.int32, device=pred.device)
-    counts = torch.zeros(B, dtype=torch.int32, device=pred.device)
-    d.pred, d.out, d.out_rows, d.counts, d.ws, d.ws_per_image = pred.data_ptr(), out.data_ptr(), rows.data_ptr(), counts.data_ptr(), ws.data_ptr(), per
-    d.B, d.N, d.no = B, N, no
-    d.conf_thres, d.iou_thres = float(conf_thres), float(iou_thres)
-    d.multi_label, d.agnostic, d.max_num = 1 if multi else 0, 1 if agnostic else 0, int(max_num)
-    d.n_classes = len(cl)
-    for i, c in enumerate(cl):
-        d.classes[i] = int(c)
-    if merge:
-        check(lib.dyk_nms_ex(ctypes.byref(d), L.NMS_MERGE, _stream()), "dyk_nms_ex")
-    else:
-        check(lib.dyk_nms(ctypes.byref(d), _stream()), "dyk_nms")
-    cnt = counts.cpu().tolist()                    # the one host sync of the eval step
+    dev = pred.device
+    out = torch.zeros((B, max_num, 6), dtype=torch.float32, device=dev)
+    rows = torch.zeros((B, max_num), dtype=torch.int32, device=dev)
+    counts = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def fill(d, ws, per):
+        d.pred, d.out, d.out_rows, d.counts, d.ws, d.ws_per_image = pred.data_ptr(), out.data_ptr(), rows.data_ptr(), counts.data_ptr(), ws.data_ptr(), per
+        d.B, d.N, d.no = B, N, no
+        d.conf_thres, d.iou_thres = float(conf_thres), float(iou_thres)
+        d.multi_label, d.agnostic, d.max_num = 1 if multi else 0, 1 if agnostic else 0, int(max_num)
+        d.n_classes = len(cl)
+        for i, c in enumerate(cl):
+            d.classes[i] = int(c)
+
+    cnt = None
+    if multi and nc >= NMS_ROWS_MIN_NC:
+        cap = nms_default_candidates(N) if candidates is None else int(candidates)
+        per = int(lib.dyk_nms_rows_workspace_bytes(N, cap))
+        ws = torch.empty(B * per, dtype=torch.uint8, device=dev)
+        n_cand = torch.empty(B, dtype=torch.int32, device=dev)
+        d = L.DykNmsRowsDesc()
+        fill(d, ws, per)
+        d.cand_cap, d.n_cand = cap, n_cand.data_ptr()
+        check(lib.dyk_nms_rows(ctypes.byref(d), L.NMS_MERGE if merge else 0, _stream()), "dyk_nms_rows")
+        _nms_routes["rows"] += 1
+        cnt = counts.cpu().tolist()                # the one host sync of the eval step
+        if min(cnt) < 0:                           # an image has more candidates than `cap`: nothing of it was written
+            _nms_routes["rows_overflow"] += 1
+            cnt = None
+            del ws
+    if cnt is None:
+        per = int(lib.dyk_nms_workspace_bytes(N, no, 1 if multi else 0))
+        ws = torch.empty(B * per, dtype=torch.uint8, device=dev)
+        d = L.DykNmsDesc()
+        fill(d, ws, per)
+        if merge:
+            check(lib.dyk_nms_ex(ctypes.byref(d), L.NMS_MERGE, _stream()), "dyk_nms_ex")
+        else:
+            check(lib.dyk_nms(ctypes.byref(d), _stream()), "dyk_nms")
+        _nms_routes["image"] += 1
+        cnt = counts.cpu().tolist()                # the one host sync of the eval step
     res = [out[b, :n] if n else None for b, n in enumerate(cnt)]
     if return_rows:
         return res, [rows[b, :n].long() if n else None for b, n in enumerate(cnt)]

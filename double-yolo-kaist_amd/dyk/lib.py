@@ -240,6 +240,11 @@ class DykNmsDesc(ctypes.Structure):
                 ("classes", _i32 * 16)]
 
 
+class DykNmsRowsDesc(ctypes.Structure):
+    # DykNmsDesc's fields, then the candidate capacity of one image and the exact candidate counts (dyk_nms_rows)
+    _fields_ = DykNmsDesc._fields_ + [("cand_cap", _i32), ("n_cand", _vp)]
+
+
 _lib = None
 _P = ctypes.POINTER
 
@@ -309,6 +314,8 @@ SIGNATURES = {
     "dyk_nms_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "dyk_nms": (_i32, [_P(DykNmsDesc), _vp]),
     "dyk_nms_ex": (_i32, [_P(DykNmsDesc), _i32, _vp]),
+    "dyk_nms_rows_workspace_bytes": (_i64, [_i32, _i32]),
+    "dyk_nms_rows": (_i32, [_P(DykNmsRowsDesc), _i32, _vp]),
     "dyk_adam_step": (_i32, [_P(DykOptimDesc), _vp]),
     "dyk_sgd_step": (_i32, [_P(DykOptimDesc), _vp]),
     "dyk_grad_stats_ws_bytes": (_i64, [_i64]),

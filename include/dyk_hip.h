@@ -788,6 +788,46 @@ int dyk_nms(const DykNmsDesc* desc, void* stream);
 int dyk_nms_ex(const DykNmsDesc* desc, int32_t flags, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Multi-label non_max_suppression with a bounded workspace (the `multi_label` branch of build_utils/utils.py:422-424,
+ * `(x[:, 5:] > conf_thres).nonzero()`, in front of the same :430-431, :446-454 as above).  dyk_nms_ex with
+ * multi_label = 1 sizes its workspace for N * nc candidates and visits every (row, class) pair with a thread of its
+ * own; dyk_nms_rows holds at most cand_cap candidates per image and walks each alive row with one wavefront, 64
+ * consecutive class scores per load.  One workgroup per image.  The descriptor's leading fields are DykNmsDesc's with
+ * the same meaning.  The argument checks are those of dyk_nms_ex plus cand_cap >= 1, n_cand != NULL, the workspace size,
+ * and multi_label != 0 with no > 6: a best-class call has one candidate per row at most and stays with dyk_nms_ex
+ * (DYK_ERR_ARG here).  Per image b:
+ *   n_cand[b] = exact number of candidates (rows x classes that pass every filter), always written;
+ *   n_cand[b] <= cand_cap: counts[b], out[b], out_rows[b] are bit for bit those of dyk_nms_ex(desc, flags) -- the
+ *                candidates are the same set in the same (row, class) order with the same fp32 bits, and sort,
+ *                suppression and merge are the same device code (csrc/nms_phases.h);
+ *   n_cand[b] >  cand_cap: counts[b] = -1 and nothing else of the image is written (out, out_rows, and the workspace
+ *                beyond the per-row arrays); the other images are not affected.  The caller repeats the batch through
+ *                dyk_nms_ex, or with cand_cap >= max(n_cand).
+ * ws: B * ws_per_image bytes, ws_per_image >= dyk_nms_rows_workspace_bytes(N, cand_cap)
+ *   = dyk_nms_workspace_bytes(cand_cap, 6, 0) + roundup(8 * N, 256)
+ *   = roundup(8 * P(cand_cap) + 28 * cand_cap, 256) + roundup(8 * N, 256),  P(c) the power of two >= c:
+ * the sort keys and candidates of a best-class call over cand_cap rows, then rowlist[N] (alive rows, ascending) and
+ * rowoff[N] (candidates per alive row, then their exclusive prefix sum).  No class count in it.
+ * ---------------------------------------------------------------------------------- */
+typedef struct DykNmsRowsDesc {
+    const float* pred;
+    float* out;            /* [B][max_num][6] */
+    int32_t* out_rows;     /* [B][max_num] */
+    int32_t* counts;       /* [B]; -1: the image has more than cand_cap candidates */
+    void* ws;
+    int64_t ws_per_image;
+    int32_t B, N, no;
+    float conf_thres, iou_thres;
+    int32_t multi_label, agnostic, max_num;
+    int32_t n_classes;     /* 0 = no class filter */
+    int32_t classes[16];
+    int32_t cand_cap;      /* candidates one image may hold in ws */
+    int32_t* n_cand;       /* [B] out: exact candidate count of the image */
+} DykNmsRowsDesc;
+int64_t dyk_nms_rows_workspace_bytes(int32_t N, int32_t cand_cap);
+int dyk_nms_rows(const DykNmsRowsDesc* desc, int32_t flags, void* stream);   /* flags: DYK_NMS_MERGE or 0 */
+
+/* ------------------------------------------------------------------------------------
  * Fused optimizer step over the flat parameter store (replaces the per-tensor torch.optim.Adam /
  * optim.SGD(nesterov=True) updates of reference train.py:85-91; same update rule incl. L2
  * weight_decay added to the gradient).  n must be a multiple of 4, pointers 16-byte aligned.
