@@ -227,7 +227,7 @@ def build_targets(p, targets, model):
 
 
 def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=True, classes=None, agnostic=False,
-                        max_num=100, merge=None, candidates=None):
+                        max_num=100, merge=None, candidates=None, return_padded=False):
     from dyk import detect
     return detect.non_max_suppression(prediction, conf_thres, iou_thres, multi_label, classes, agnostic, max_num, merge=merge,
-                                      candidates=candidates)
+                                      candidates=candidates, return_padded=return_padded)

@@ -8,6 +8,7 @@
 // tensor is converted in place on its first four columns).
 #pragma clang fp contract(off)
 #include "dyk_common.h"
+#include "box_scale.h"
 
 namespace {
 
@@ -24,19 +25,14 @@ __global__ void box_convert_kernel(const float* __restrict__ in, float* __restri
     }
 }
 
-__device__ inline float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }   // NaN passes through like torch.clamp_
-
 __global__ void scale_coords_kernel(float* __restrict__ boxes, int n, int ld, float pad_x, float pad_y, float gain,
                                     float w0, float h0, int do_scale) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         float* b = boxes + (long)i * ld;
         float x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
-        if (do_scale) {
-            x1 = (x1 - pad_x) / gain; x2 = (x2 - pad_x) / gain;
-            y1 = (y1 - pad_y) / gain; y2 = (y2 - pad_y) / gain;
-        }
-        b[0] = clampf(x1, 0.f, w0); b[1] = clampf(y1, 0.f, h0);
-        b[2] = clampf(x2, 0.f, w0); b[3] = clampf(y2, 0.f, h0);
+        if (do_scale) unletterbox(x1, y1, x2, y2, pad_x, pad_y, gain);
+        clip_box(x1, y1, x2, y2, w0, h0);
+        b[0] = x1; b[1] = y1; b[2] = x2; b[3] = y2;
     }
 }
 

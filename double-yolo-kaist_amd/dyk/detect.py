@@ -1,5 +1,5 @@
 """Host side of the loss / target-assignment / NMS kernels (dyk_yolo_loss, dyk_build_targets, dyk_nms, dyk_nms_ex,
-dyk_nms_rows)."""
+dyk_nms_rows).  The evaluator that consumes the NMS output is dyk/evalmap.py."""
 import ctypes
 import os
 
@@ -213,7 +213,7 @@ def nms_default_candidates(N):
 
 
 def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=True, classes=None, agnostic=False,
-                        max_num=100, return_rows=False, merge=None, candidates=None):
+                        max_num=100, return_rows=False, merge=None, candidates=None, return_padded=False):
     """reference build_utils/utils.py:387-464 -> list (per image) of [n,6] tensors or None.
 
     merge: the reference's `merge` setting (utils.py:398, False as shipped; :450-454): every kept box becomes the
@@ -223,7 +223,11 @@ def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=T
 
     candidates: multi-label calls (multi_label and more than one class) hold at most this many candidates per image in
     their workspace (dyk_nms_rows); None = max(N, 8192).  An image with more makes the call run the batch again with the
-    workspace for N * nc candidates (dyk_nms / dyk_nms_ex), so the result never depends on it."""
+    workspace for N * nc candidates (dyk_nms / dyk_nms_ex), so the result never depends on it.
+
+    return_padded: hand back (out [B, max_num, 6], counts) instead of the list -- the kernel's own output and the counts this
+    call has read anyway (an overflowed-and-rerun image never shows its -1), the form dyk.evalmap.DetectionEvaluator.update
+    takes without touching a tensor.  The launches are the same either way."""
     if merge is None:
         merge = os.environ.get("DYK_NMS_MERGE", "0") not in ("", "0")
     cl = list(classes) if classes else []
@@ -279,6 +283,8 @@ def non_max_suppression(prediction, conf_thres=0.1, iou_thres=0.6, multi_label=T
             check(lib.dyk_nms(ctypes.byref(d), _stream()), "dyk_nms")
         _nms_routes["image"] += 1
         cnt = counts.cpu().tolist()                # the one host sync of the eval step
+    if return_padded:
+        return out, cnt
     res = [out[b, :n] if n else None for b, n in enumerate(cnt)]
     if return_rows:
         return res, [rows[b, :n].long() if n else None for b, n in enumerate(cnt)]

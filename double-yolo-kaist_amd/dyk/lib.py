@@ -245,6 +245,17 @@ class DykNmsRowsDesc(ctypes.Structure):
     _fields_ = DykNmsDesc._fields_ + [("cand_cap", _i32), ("n_cand", _vp)]
 
 
+EVAL_MAX_THR = 16          # DYK_EVAL_MAX_THR (include/dyk_hip.h): IoU thresholds of one dyk_eval_match launch
+EVAL_MAX_GT = 1024         # DYK_EVAL_MAX_GT: ground-truth boxes of one image
+
+
+class DykEvalMatchDesc(ctypes.Structure):
+    _fields_ = [("out", _vp), ("counts", _vp), ("rec_off", _vp), ("targets", _vp), ("gt_off", _vp), ("shape0", _vp),
+                ("unpad", _vp), ("conf", _vp), ("cls", _vp), ("tp_mask", _vp), ("match", _vp), ("iou", _vp), ("box", _vp),
+                ("err", _vp), ("thr", ctypes.c_double * EVAL_MAX_THR), ("B", _i32), ("max_num", _i32), ("nt", _i32),
+                ("nc", _i32), ("T", _i32), ("rec_cap", _i32)]
+
+
 _lib = None
 _P = ctypes.POINTER
 
@@ -337,6 +348,7 @@ SIGNATURES = {
     "dyk_stem_wgrad_bn_fusable": (_i32, [_P(DykStemDesc)]),
     "dyk_box_convert": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dyk_scale_coords": (_i32, [_vp, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "dyk_eval_match": (_i32, [_P(DykEvalMatchDesc), _vp]),
 }
 
 

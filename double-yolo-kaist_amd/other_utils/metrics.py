@@ -7,6 +7,10 @@ Differences from the reference, both deliberate:
   * `labels` is not modified (the reference rewrites the caller's arrays in place, so it can be called once only);
   * the per-prediction IoU row and the curve post-processing are vectorised; the greedy matching stays sequential
     because a ground truth claimed by a higher-scoring detection turns later matches into false positives.
+
+`compute_map` (not in the reference, whose multi-class number comes from a pycocotools wrapper) is the host half of the
+multi-class evaluator dyk.evalmap.DetectionEvaluator: per-class AP / LAMR at several IoU thresholds and their means from the
+per-detection match records dyk_eval_match writes on the device, through the same `voc_ap` / `log_average_miss_rate`.
 """
 import math
 
@@ -80,3 +84,55 @@ def compute_ap_lamr(preds, labels, shapes):
     ap = voc_ap(recall, precision)
     lamr, fppi, mr = log_average_miss_rate(recall, fp_cum, len(labels))
     return {"recall": recall, "precision": precision, "fppi": fppi, "mr": mr, "ap": ap, "lamr": lamr}
+
+
+def compute_map(conf, cls, tp_mask, n_gt_per_class, num_imgs, iou_thresholds=(0.5,), names=None):
+    """Per-class AP / LAMR at one or several IoU thresholds, and their means, from per-detection match records.
+
+    conf [n] scores, cls [n] class indices, tp_mask [n] uint32 with bit t set when the detection is a true positive at
+    iou_thresholds[t] -- the records of dyk.evalmap.DetectionEvaluator (dyk_eval_match), in append order: image, then
+    rank within the image.  n_gt_per_class [nc] ground-truth boxes per class, num_imgs the images evaluated.
+
+    The records are sorted stably by descending conf (what Python's stable sort(reverse=True) gives evaluate.py:114:
+    equal scores keep append order); per class and threshold the cumulative TP / FP, recall and precision go through
+    `voc_ap` and `log_average_miss_rate` above.  Returns a dict:
+      ap, lamr [nc, T]     nan for a class without ground truth, AP 0 / LAMR 1 for one with ground truth and no detection
+      map                  mean of ap over the thresholds and the classes that have ground truth (nan when none has)
+      map50                the same at the threshold 0.5 (key present only when 0.5 is among iou_thresholds)
+      recall, precision    [nc][T] lists of the per-detection curves
+      summary              the table as text, rows labelled by `names`
+
+    This is the VOC / KAIST rule of compute_ap_lamr applied per class: a detection is matched to the box of its class
+    with the largest IoU (np.argmax) and is a false positive when that box is already claimed -- not COCO's
+    best-unclaimed rule; AP is the continuous `voc_ap` integral, not COCO's 101-point interpolation; there are no crowd
+    regions and no area ranges.  The numbers are therefore not comparable with published COCO figures."""
+    conf, cls, tp_mask = np.asarray(conf), np.asarray(cls).astype(np.int64), np.asarray(tp_mask).astype(np.uint32)
+    n_gt = np.asarray(n_gt_per_class, dtype=np.int64)
+    nc, T = n_gt.shape[0], len(iou_thresholds)
+    order = np.argsort(-conf.astype(np.float64), kind="stable")
+    cls, tp_mask = cls[order], tp_mask[order]
+    ap, lamr = np.full((nc, T), np.nan), np.full((nc, T), np.nan)
+    recall = [[None] * T for _ in range(nc)]
+    precision = [[None] * T for _ in range(nc)]
+    for c in np.nonzero(n_gt > 0)[0]:
+        bits = tp_mask[cls == c]
+        for t in range(T):
+            tp = ((bits >> np.uint32(t)) & np.uint32(1)).astype(np.int32)
+            tp_cum, fp_cum = np.cumsum(tp), np.cumsum(1 - tp)
+            rec = tp_cum / n_gt[c]
+            prec = tp_cum / (tp_cum + fp_cum)
+            recall[c][t], precision[c][t] = rec, prec
+            ap[c, t] = voc_ap(rec, prec)
+            lamr[c, t] = log_average_miss_rate(rec, fp_cum, num_imgs)[0]
+    has = n_gt > 0
+    res = {"ap": ap, "lamr": lamr, "recall": recall, "precision": precision,
+           "map": float(ap[has].mean()) if has.any() else float("nan")}
+    at50 = [t for t, v in enumerate(iou_thresholds) if float(v) == 0.5]
+    if at50:
+        res["map50"] = float(ap[has, at50[0]].mean()) if has.any() else float("nan")
+    label = (lambda c: str(names[c])) if names is not None else (lambda c: "class %d" % c)
+    rows = ["%-20s %8s %8s %8s" % ("class", "boxes", "AP@%.2f" % float(iou_thresholds[0]), "AP mean")]
+    rows += ["%-20s %8d %8.4f %8.4f" % (label(c), n_gt[c], ap[c, 0], ap[c].mean()) for c in range(nc)]
+    rows.append("%-20s %8d %8s %8.4f" % ("all (VOC-style mAP)", n_gt.sum(), "", res["map"]))
+    res["summary"] = "\n".join(rows)
+    return res

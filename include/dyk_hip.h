@@ -1149,6 +1149,56 @@ int dyk_box_convert(const float* in, float* out, int32_t n, int32_t ld_in, int32
 int dyk_scale_coords(float* boxes, int32_t n, int32_t ld, float pad_x, float pad_y, float gain, float w0, float h0,
                      int32_t do_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Matching of one evaluation batch's detections to its ground truth, per class and per IoU threshold (replaces the
+ * per-batch half of the evaluation: other_utils/metrics.py box_iou :62-79 and the matching loop of compute_ap_lamr
+ * :81-130, the caller's loop evaluate.py:76-106, scale_coords / clip_coords build_utils/utils.py:60-92).  One launch,
+ * one wavefront per image, no allocation, no atomics, no synchronisation; the curve arithmetic (once per epoch) stays
+ * on the host (other_utils.metrics.compute_map).
+ *
+ * Reads   out [B][max_num][6] (x1,y1,x2,y2,conf,cls) and counts [B] as dyk_nms leaves them (counts[b] <= 0: no detection),
+ *         rec_off [B]   first record of image b; records [rec_off[b], rec_off[b] + counts[b]) must lie inside rec_cap,
+ *         targets [nt][6] (image in batch, class, xc, yc, w, h; relative), sorted by image: image b owns rows
+ *         [gt_off[b], gt_off[b+1]), at most DYK_EVAL_MAX_GT of them,
+ *         shape0 [B][2] original (width, height), unpad [B][4] (pad_x, pad_y, gain, do_scale) or NULL (boxes as they are).
+ * Per image, type for type the arithmetic of the host evaluator, so every decision is the same decision:
+ *   ground truth  fp32, no FMA: x *= w0, y *= h0, x1 = xc - w / 2, x2 = w + x1 (likewise y), truncated to int32;
+ *   detections    do_scale != 0: (x - pad) / gain, clamped to [0, w0] / [0, h0] -- the expressions of dyk_scale_coords;
+ *   IoU           pixel-inclusive (+1); detection area in fp32, ground-truth area in int32, everything else in fp64
+ *                 after exact conversion: extents, clip to [0, 1e5], product, inter / (a1 + a2 - inter).
+ * Detections are walked in NMS order.  For detection d of class c: k = the box of class c in the image with the largest
+ * IoU, the lowest index among equals (np.argmax); for every threshold t: tp_t = iou >= thr[t] && !claimed_t[k], and a true
+ * tp_t claims k at t.  A best box that is already claimed makes d a false positive at t (no second choice).  No box of
+ * class c in the image: tp_mask 0, match -1, iou 0.  A class outside [0, nc): the same record and err[0] = 1.  An image
+ * whose table entries are out of range (records outside rec_cap, rows outside nt, more than DYK_EVAL_MAX_GT rows) writes
+ * nothing and sets err[1] = 1.  err [2] is only ever set, with plain stores of the same word; the caller clears it.
+ * Writes, per detection r = rec_off[b] + rank: conf[r], cls[r], tp_mask[r] (bit t), match[r] (row of `targets` or -1),
+ * iou[r] (the best one, fp64), box[r][4] (the box the IoU was taken of).
+ * DYK_ERR_ARG before any launch: a null pointer (unpad and targets with nt == 0 excepted), B < 1, max_num < 1, nc < 1,
+ * T outside [1, DYK_EVAL_MAX_THR], nt < 0, rec_cap < 0.
+ * ---------------------------------------------------------------------------------- */
+#define DYK_EVAL_MAX_THR 16
+#define DYK_EVAL_MAX_GT 1024
+typedef struct DykEvalMatchDesc {
+    const float* out;
+    const int32_t* counts;
+    const int32_t* rec_off;
+    const float* targets;
+    const int32_t* gt_off;
+    const int32_t* shape0;
+    const float* unpad;
+    float* conf;
+    int32_t* cls;
+    uint32_t* tp_mask;
+    int32_t* match;
+    double* iou;
+    float* box;
+    int32_t* err;
+    double thr[DYK_EVAL_MAX_THR];
+    int32_t B, max_num, nt, nc, T, rec_cap;
+} DykEvalMatchDesc;
+int dyk_eval_match(const DykEvalMatchDesc* desc, void* stream);
+
 /* Profiling variant of dyk_run_commands: brackets every command with HIP events on `stream`
  * and, after synchronising the stream, writes each command's duration in milliseconds to
  * ms_out[0..n).  Used by bench.py's roofline pass, never in a timed throughput region. */
