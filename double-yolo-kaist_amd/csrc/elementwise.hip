@@ -1,7 +1,7 @@
 // HBM-bound channels-last kernels around the convolutions: axpby (copy / add / weighted
 // feature fusion), nearest 2x upsample, max-pool with arg-max, squeeze-excitation, YOLO head
 // permute, first-layer patch gather.  Forward and backward of each.
-#include "dyk_common.h"
+#include "ew_strip.h"
 
 namespace {
 
@@ -9,7 +9,6 @@ inline int ew_grid(long total_vec) {
     long g = (total_vec + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
-inline int epv_of(int dtype) { return dtype == DYK_F32 ? 4 : 8; }
 
 // ------------------------------------------------------------------ axpby
 // out = sa*a (+ sb*b), sa = alpha * (p0 ? p0[0] : 1), sb = beta * (p1 ? p1[0] : 1).  alpha == 0: `a` is NOT read (the term is an
@@ -301,6 +300,16 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(DykEwDesc d, const uin
 //             the k*k scan above, for 2k instead of k*k loads per output (13 x 13: 43 -> 8 us per launch).
 //   backward  the k*k gather of the kernel above, same (dy, dx) order -- same bits -- from an LDS copy of the gradient and
 //             argmax planes.
+// The arg-max codes of a vector's EPV elements travel through LDS and to `idx` one byte each, element j in byte j of a uint2.
+__device__ inline uint32_t amax_code(uint2 v, int j) { return ((j < 4 ? v.x : v.y) >> (8 * (j & 3))) & 0xffu; }
+template <int EPV> __device__ inline uint2 amax_pack(const uint32_t* code) {
+    uint2 pk = make_uint2(0u, 0u);
+#pragma unroll
+    for (int j = 0; j < EPV; ++j) {
+        if (j < 4) pk.x |= code[j] << (8 * j); else pk.y |= code[j] << (8 * (j - 4));
+    }
+    return pk;
+}
 template <typename T>
 __global__ __launch_bounds__(1024) void maxpool_tile_fwd_kernel(DykEwDesc d, uint8_t* __restrict__ idx) {
     constexpr int EPV = ElemTraits<T>::EPV;
@@ -331,12 +340,7 @@ __global__ __launch_bounds__(1024) void maxpool_tile_fwd_kernel(DykEwDesc d, uin
             first = false;
         }
         rmax[p] = vec_pack<T>(m);                // (exact: the maxima are elements of the tile)
-        uint2 pk = make_uint2(0u, 0u);
-#pragma unroll
-        for (int j = 0; j < EPV; ++j) {
-            if (j < 4) pk.x |= mi[j] << (8 * j); else pk.y |= mi[j] << (8 * (j - 4));
-        }
-        radx[p] = pk;
+        radx[p] = amax_pack<EPV>(mi);
     }
     __syncthreads();
     T* __restrict__ o = (T*)d.out + (long)b * HW * d.ldo + c;
@@ -354,20 +358,16 @@ __global__ __launch_bounds__(1024) void maxpool_tile_fwd_kernel(DykEwDesc d, uin
             for (int j = 0; j < EPV; ++j)
                 if (first || t[j] > m[j] || t[j] != t[j]) {
                     m[j] = t[j];
-                    mi[j] = (uint32_t)(dy * k) + (((j < 4 ? ax.x : ax.y) >> (8 * (j & 3))) & 0xffu);
+                    mi[j] = (uint32_t)(dy * k) + amax_code(ax, j);
                 }
             first = false;
         }
         *(uint4*)(o + (long)p * d.ldo) = vec_pack<T>(m);
         if (idx) {
             uint8_t* ip = idx + ((long)b * HW + p) * d.C + c;
-            uint32_t lo = 0u, hi = 0u;
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) {
-                if (j < 4) lo |= mi[j] << (8 * j); else hi |= mi[j] << (8 * (j - 4));
-            }
-            *(uint32_t*)ip = lo;                 // (C % 4 == 0: aligned)
-            if (EPV > 4) *(uint32_t*)(ip + 4) = hi;
+            const uint2 pk = amax_pack<EPV>(mi);
+            *(uint32_t*)ip = pk.x;               // (C % 4 == 0: aligned)
+            if (EPV > 4) *(uint32_t*)(ip + 4) = pk.y;
         }
     }
 }
@@ -420,18 +420,13 @@ __global__ __launch_bounds__(1024) void maxpool_tile_bwd_kernel(DykEwDesc d, con
             const uint32_t lo = (uint32_t)(dy * k);
 #pragma unroll
             for (int j = 0; j < EPV; ++j) {
-                const uint32_t code = (((j < 4 ? ix.x : ix.y) >> (8 * (j & 3))) & 0xffu) - lo;     // dx if this output selects row yy
+                const uint32_t code = amax_code(ix, j) - lo;     // dx if this output selects row yy
                 if (code < (uint32_t)k) { r[j] += g[j]; dxs[j] = code; }
             }
         }
         rg[2 * p] = make_float4(r[0], r[1], r[2], r[3]);
         if (EPV > 4) rg[2 * p + 1] = make_float4(r[4 % EPV], r[5 % EPV], r[6 % EPV], r[7 % EPV]);
-        uint2 pk = make_uint2(0u, 0u);
-#pragma unroll
-        for (int j = 0; j < EPV; ++j) {
-            if (j < 4) pk.x |= dxs[j] << (8 * j); else pk.y |= dxs[j] << (8 * (j - 4));
-        }
-        rd[p] = pk;
+        rd[p] = amax_pack<EPV>(dxs);
     }
     __syncthreads();
     T* __restrict__ o = (T*)d.out + (long)b * HW * d.ldo + c;
@@ -451,7 +446,7 @@ __global__ __launch_bounds__(1024) void maxpool_tile_bwd_kernel(DykEwDesc d, con
             const float r[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
 #pragma unroll
             for (int j = 0; j < EPV; ++j)
-                if ((((j < 4 ? ix.x : ix.y) >> (8 * (j & 3))) & 0xffu) == (uint32_t)dx) s[j] += r[j];
+                if (amax_code(ix, j) == (uint32_t)dx) s[j] += r[j];
         }
         if (accum) {
             float t[EPV];
@@ -480,7 +475,8 @@ __global__ __launch_bounds__(256) void se_pool_kernel(DykEwDesc d, float* __rest
     const int b = blockIdx.y;
     const int HW = d.H * d.W;
     const bool active = cv < CV;
-    float s[EPV];
+    float sum[1][EPV];
+    float (&s)[EPV] = sum[0];
 #pragma unroll
     for (int j = 0; j < EPV; ++j) s[j] = 0.f;
     if (active) {
@@ -518,16 +514,7 @@ __global__ __launch_bounds__(256) void se_pool_kernel(DykEwDesc d, float* __rest
             }
         }
     }
-    float* mine = red + threadIdx.x * 8;
-#pragma unroll
-    for (int j = 0; j < EPV; ++j) mine[j] = s[j];
-    __syncthreads();
-    if (ty == 0 && active) {
-        for (int q = 1; q < PY; ++q) {
-            const float* o = red + (q * CVB + tx) * 8;
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) s[j] += o[j];
-        }
+    if (strip_fold<1>(red, sum, CVB, PY, tx, ty, active)) {
         if (gridDim.z > 1) {
             float* part = (float*)d.aux2 + ((long)blockIdx.z * d.B + b) * d.C + c;
 #pragma unroll
@@ -711,12 +698,12 @@ __global__ __launch_bounds__(256) void se_scale_kernel(DykEwDesc d, int CVB) {
     if (!RED && !active) return;
     const int c = active ? cv * EPV : 0;
     const int HW = d.H * d.W;
-    float sc[EPV], sh[EPV], mu[EPV], rs[EPV], s1[EPV], s2[EPV];
+    float sc[EPV], sh[EPV], mu[EPV], rs[EPV], sum[2][EPV];          // sum(da), sum(da * xhat)
     if constexpr (RED) {
 #pragma unroll
         for (int j = 0; j < EPV; ++j) {
             sc[j] = d.p2[c + j]; sh[j] = d.p2[d.C + c + j]; mu[j] = d.p2[2 * d.C + c + j]; rs[j] = d.p2[3 * d.C + c + j];
-            s1[j] = s2[j] = 0.f;
+            sum[0][j] = sum[1][j] = 0.f;
         }
     }
     const bool accum = d.flags & DYK_EW_ACCUM;
@@ -773,9 +760,10 @@ __global__ __launch_bounds__(256) void se_scale_kernel(DykEwDesc d, int CVB) {
                     vec_unpack<T>(vy[u], yy);
 #pragma unroll
                     for (int j = 0; j < EPV; ++j) {
-                        const float da = g[j] * act_bwd_c<ACT>(yy[j] * sc[j] + sh[j], d.act);
-                        s1[j] += da;
-                        s2[j] += da * ((yy[j] - mu[j]) * rs[j]);
+                        float da, xh;
+                        bn_bwd_terms<ACT>(g[j], yy[j], sc[j], sh[j], mu[j], rs[j], d.act, da, xh);
+                        sum[0][j] += da;
+                        sum[1][j] += da * xh;
                     }
                 }
             }
@@ -783,24 +771,7 @@ __global__ __launch_bounds__(256) void se_scale_kernel(DykEwDesc d, int CVB) {
     }
     if constexpr (RED) {
         // pixel lanes through LDS in lane order, then one fp64 atomic per channel and sum into this workgroup's replica
-        float* mine = red + threadIdx.x * 2 * 8;
-#pragma unroll
-        for (int j = 0; j < EPV; ++j) { mine[j] = s1[j]; mine[8 + j] = s2[j]; }
-        __syncthreads();
-        if (ty == 0 && active) {
-            for (int q = 1; q < PY; ++q) {
-                const float* oo = red + (q * CVB + tx) * 2 * 8;
-#pragma unroll
-                for (int j = 0; j < EPV; ++j) { s1[j] += oo[j]; s2[j] += oo[8 + j]; }
-            }
-            const unsigned wgi = blockIdx.z * gridDim.y + blockIdx.y;
-            double* rd = d.red + (size_t)(wgi % (unsigned)(d.slots > 0 ? d.slots : 1)) * 2 * d.C;
-#pragma unroll
-            for (int j = 0; j < EPV; ++j) {
-                atomicAdd(rd + c + j, (double)s1[j]);
-                atomicAdd(rd + d.C + c + j, (double)s2[j]);
-            }
-        }
+        if (strip_fold<2>(red, sum, CVB, PY, tx, ty, active)) replica_atomics(d.red, d.C, c, blockIdx.z * gridDim.y + blockIdx.y, d.slots, sum);
     }
 }
 
@@ -908,55 +879,32 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const float* __restri
     }
 }
 
-int check_ew(const DykEwDesc* d, bool need_b, bool need_out = true, bool twin_ok = false) {
-    if (!d || !d->a || (need_out && !d->out) || (need_b && !d->b)) return DYK_ERR_ARG;
-    if (d->twin && !twin_ok) return DYK_ERR_UNSUPPORTED;      // two-problem launches: BatchNorm passes and axpby only
-    if (d->dtype != DYK_BF16 && d->dtype != DYK_F32 && d->dtype != DYK_F16) return DYK_ERR_ARG;
-    const int epv = epv_of(d->dtype);
-    if (d->C <= 0 || d->C % epv || d->lda % epv || (need_out && d->ldo % epv) || (d->b && d->ldb % epv)) return DYK_ERR_ARG;
-    return DYK_OK;
-}
-
 }  // namespace
 
-// DISPATCH_T: training kernels (bf16 | f32; f16 is the inference type: DYK_ERR_UNSUPPORTED); DISPATCH_TF: the forward
-// kernels an inference plan issues (bf16 | f16 | f32)
-#define DISPATCH_TF(kern, grid, block, lds, stream, ...)                                             \
-    do {                                                                                             \
-        if (d->dtype == DYK_BF16) hipLaunchKernelGGL(kern<bf16_t>, grid, block, lds, stream, __VA_ARGS__); \
-        else if (d->dtype == DYK_F16) hipLaunchKernelGGL(kern<f16_t>, grid, block, lds, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kern<float>, grid, block, lds, stream, __VA_ARGS__);                 \
-        DYK_LAUNCH_CHECK();                                                                          \
-    } while (0)
-#define DISPATCH_T(kern, grid, block, lds, stream, ...)                                              \
-    do {                                                                                             \
-        if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;                                         \
-        if (d->dtype == DYK_BF16) hipLaunchKernelGGL(kern<bf16_t>, grid, block, lds, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kern<float>, grid, block, lds, stream, __VA_ARGS__);                 \
-        DYK_LAUNCH_CHECK();                                                                          \
-    } while (0)
-
+// Every launcher ends in ew_launch_dtype<F16_OK> (ew_strip.h): the forward kernels an inference plan issues take bf16 | f16 | f32;
+// the training kernels bf16 | f32, and DYK_ERR_UNSUPPORTED for f16 comes back from there.
 extern "C" int dyk_axpby(const DykEwDesc* d, void* stream) {
-    const int rc = check_ew(d, false, true, true);
+    const int rc = ew_check(d, true, false, true, true);
     if (rc) return rc;
-    if (d->npix <= 0) return DYK_ERR_ARG;
-    const int grid = ew_grid((long)d->npix * (d->C / epv_of(d->dtype)));
+    const int grid = ew_grid((long)d->npix * (d->C / ew_epv(d->dtype)));
     DykEwPair pr;
     const int nz = dyk_fill_ew_pair(pr, d);
     if (!nz) return DYK_ERR_ARG;
-    DISPATCH_TF(axpby_kernel, dim3(grid, 1, nz), dim3(256), 0, (hipStream_t)stream, pr);
-    return DYK_OK;
+    return ew_launch_dtype<true>(d->dtype, [&](auto t) {
+        hipLaunchKernelGGL(axpby_kernel<ew_t<decltype(t)>>, dim3(grid, 1, nz), dim3(256), 0, (hipStream_t)stream, pr);
+    });
 }
 
 extern "C" int dyk_dot(const DykEwDesc* d, void* stream) {
-    const int rc = check_ew(d, true, false);
+    const int rc = ew_check(d, false, true, false, true);
     if (rc) return rc;
-    if (d->npix <= 0 || !d->red || (d->out && d->ldo % epv_of(d->dtype))) return DYK_ERR_ARG;
-    long g = ((long)d->npix * (d->C / epv_of(d->dtype)) + 256 * 8 - 1) / (256 * 8);
+    if (!d->red || (d->out && d->ldo % ew_epv(d->dtype))) return DYK_ERR_ARG;
+    long g = ((long)d->npix * (d->C / ew_epv(d->dtype)) + 256 * 8 - 1) / (256 * 8);
     if (g > 1024) g = 1024;
     if (g < 1) g = 1;
-    DISPATCH_T(dot_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, *d);
-    return DYK_OK;
+    return ew_launch_dtype<false>(d->dtype, [&](auto t) {
+        hipLaunchKernelGGL(dot_kernel<ew_t<decltype(t)>>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, *d);
+    });
 }
 
 extern "C" int dyk_wfuse_weights(const float* w, float* weff, int32_t n, void* stream) {
@@ -974,41 +922,27 @@ extern "C" int dyk_wfuse_bwd_params(const float* w, const double* red, float* dw
 }
 
 extern "C" int dyk_upsample2x_fwd(const DykEwDesc* d, void* stream) {
-    const int rc = check_ew(d, false);
+    const int rc = ew_check(d, true, false, false, false);
     if (rc) return rc;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0) return DYK_ERR_ARG;
-    const int grid = ew_grid((long)d->B * d->H * d->W * 4 * (d->C / epv_of(d->dtype)));
-    DISPATCH_TF(upsample2x_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
-    return DYK_OK;
+    const int grid = ew_grid((long)d->B * d->H * d->W * 4 * (d->C / ew_epv(d->dtype)));
+    return ew_launch_dtype<true>(d->dtype, [&](auto t) {
+        hipLaunchKernelGGL(upsample2x_fwd_kernel<ew_t<decltype(t)>>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
+    });
 }
 
 extern "C" int dyk_upsample2x_bwd(const DykEwDesc* d, void* stream) {
-    const int rc = check_ew(d, false);
+    const int rc = ew_check(d, true, false, false, false);
     if (rc) return rc;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0) return DYK_ERR_ARG;
-    const int grid = ew_grid((long)d->B * d->H * d->W * (d->C / epv_of(d->dtype)));
-    DISPATCH_T(upsample2x_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
-    return DYK_OK;
+    const int grid = ew_grid((long)d->B * d->H * d->W * (d->C / ew_epv(d->dtype)));
+    return ew_launch_dtype<false>(d->dtype, [&](auto t) {
+        hipLaunchKernelGGL(upsample2x_bwd_kernel<ew_t<decltype(t)>>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
+    });
 }
 
-#define MAXPOOL_K(kern, KK, arg, F16OK)                                                                                 \
-    do {                                                                                                         \
-        if constexpr (F16OK) { if (d->dtype == DYK_F16) { hipLaunchKernelGGL((kern<f16_t, KK>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, arg); break; } } \
-        if (d->dtype == DYK_BF16) hipLaunchKernelGGL((kern<bf16_t, KK>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, arg); \
-        else hipLaunchKernelGGL((kern<float, KK>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, arg);      \
-    } while (0)
-#define MAXPOOL_DISPATCH(kern, arg, F16OK)                                                                              \
-    do {                                                                                                         \
-        switch (d->k) {                                                                                          \
-        case 2: MAXPOOL_K(kern, 2, arg, F16OK); break;                                                                  \
-        case 3: MAXPOOL_K(kern, 3, arg, F16OK); break;                                                                  \
-        case 5: MAXPOOL_K(kern, 5, arg, F16OK); break;                                                                  \
-        case 9: MAXPOOL_K(kern, 9, arg, F16OK); break;                                                                  \
-        case 13: MAXPOOL_K(kern, 13, arg, F16OK); break;                                                                \
-        default: MAXPOOL_K(kern, 0, arg, F16OK); break;                                                                 \
-        }                                                                                                        \
-        DYK_LAUNCH_CHECK();                                                                                      \
-    } while (0)
+// the window sizes the generic max-pool kernels are instantiated for; any other k <= 15 runs the runtime-k form <T, 0>
+typedef EwInts<2, 3, 5, 9, 13> PoolKs;
 
 // the LDS-plane kernels: stride 1, odd window (output map = input map), map of at most 1024 pixels, 4-byte aligned argmax rows
 static bool maxpool_tile_ok(const DykEwDesc* d) {
@@ -1017,46 +951,51 @@ static bool maxpool_tile_ok(const DykEwDesc* d) {
 static int maxpool_tile_threads(int HW) { const int t = (HW + 63) / 64 * 64; return t > 1024 ? 1024 : t; }
 
 extern "C" int dyk_maxpool_fwd(const DykEwDesc* d, uint8_t* argmax, void* stream) {
-    const int rc = check_ew(d, false);
+    const int rc = ew_check(d, true, false, false, false);
     if (rc) return rc;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->k <= 0 || d->k > 15 || d->slots < 0 || d->slots > 8) return DYK_ERR_ARG;
     if (maxpool_tile_ok(d)) {
         const int HW = d->H * d->W, threads = maxpool_tile_threads(HW);
-        const unsigned grid = (unsigned)(d->B * (d->C / epv_of(d->dtype)));
-        if (d->dtype == DYK_F16) hipLaunchKernelGGL(maxpool_tile_fwd_kernel<f16_t>, dim3(grid), dim3(threads), (size_t)HW * 40, (hipStream_t)stream, *d, argmax);
-        else if (d->dtype == DYK_BF16) hipLaunchKernelGGL(maxpool_tile_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), (size_t)HW * 40, (hipStream_t)stream, *d, argmax);
-        else hipLaunchKernelGGL(maxpool_tile_fwd_kernel<float>, dim3(grid), dim3(threads), (size_t)HW * 40, (hipStream_t)stream, *d, argmax);
-        DYK_LAUNCH_CHECK();
-        return DYK_OK;
+        const unsigned grid = (unsigned)(d->B * (d->C / ew_epv(d->dtype)));
+        return ew_launch_dtype<true>(d->dtype, [&](auto t) {
+            hipLaunchKernelGGL(maxpool_tile_fwd_kernel<ew_t<decltype(t)>>, dim3(grid), dim3(threads), (size_t)HW * 40, (hipStream_t)stream, *d, argmax);
+        });
     }
-    const int grid = ew_grid((long)d->B * d->H * d->W * (d->C / epv_of(d->dtype)));
-    MAXPOOL_DISPATCH(maxpool_fwd_kernel, argmax, true);
-    return DYK_OK;
+    const int grid = ew_grid((long)d->B * d->H * d->W * (d->C / ew_epv(d->dtype)));
+    return ew_launch_dtype<true>(d->dtype, [&](auto t) {
+        auto launch = [&](auto K) {
+            hipLaunchKernelGGL((maxpool_fwd_kernel<ew_t<decltype(t)>, decltype(K)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, argmax);
+        };
+        if (!ew_dispatch_int(d->k, PoolKs(), launch)) launch(std::integral_constant<int, 0>());
+    });
 }
 
 extern "C" int dyk_maxpool_bwd(const DykEwDesc* d, const uint8_t* argmax, void* stream) {
-    const int rc = check_ew(d, false);
+    const int rc = ew_check(d, true, false, false, false);
     if (rc) return rc;
     if (!argmax || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->k <= 0 || d->k > 15 || d->slots < 0 || d->slots > 8) return DYK_ERR_ARG;
     if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
     if (maxpool_tile_ok(d)) {
         const int HW = d->H * d->W, threads = maxpool_tile_threads(HW);
-        const unsigned grid = (unsigned)(d->B * (d->C / epv_of(d->dtype)));
-        if (d->dtype == DYK_BF16) hipLaunchKernelGGL(maxpool_tile_bwd_kernel<bf16_t>, dim3(grid), dim3(threads), (size_t)HW * 64, (hipStream_t)stream, *d, argmax);
-        else hipLaunchKernelGGL(maxpool_tile_bwd_kernel<float>, dim3(grid), dim3(threads), (size_t)HW * 64, (hipStream_t)stream, *d, argmax);
-        DYK_LAUNCH_CHECK();
-        return DYK_OK;
+        const unsigned grid = (unsigned)(d->B * (d->C / ew_epv(d->dtype)));
+        return ew_launch_dtype<false>(d->dtype, [&](auto t) {
+            hipLaunchKernelGGL(maxpool_tile_bwd_kernel<ew_t<decltype(t)>>, dim3(grid), dim3(threads), (size_t)HW * 64, (hipStream_t)stream, *d, argmax);
+        });
     }
-    const int grid = ew_grid((long)d->B * d->H * d->W * (d->C / epv_of(d->dtype)));
-    MAXPOOL_DISPATCH(maxpool_bwd_kernel, argmax, false);       // (f16 refused above: no backward forms)
-    return DYK_OK;
+    const int grid = ew_grid((long)d->B * d->H * d->W * (d->C / ew_epv(d->dtype)));
+    return ew_launch_dtype<false>(d->dtype, [&](auto t) {
+        auto launch = [&](auto K) {
+            hipLaunchKernelGGL((maxpool_bwd_kernel<ew_t<decltype(t)>, decltype(K)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d, argmax);
+        };
+        if (!ew_dispatch_int(d->k, PoolKs(), launch)) launch(std::integral_constant<int, 0>());
+    });
 }
 
 extern "C" int dyk_se_pool(const DykEwDesc* d, float* pooled, void* stream) {
-    const int rc = check_ew(d, false, false);
+    int rc = ew_check(d, false, false, false, false);
     if (rc) return rc;
     if (!pooled || d->B <= 0 || d->H <= 0 || d->W <= 0) return DYK_ERR_ARG;
-    const int CV = d->C / epv_of(d->dtype);
+    const int CV = d->C / ew_epv(d->dtype);
     int CVB = 1;
     while (CVB < CV && CVB < 16) CVB <<= 1;
     const int gx = (CV + CVB - 1) / CVB, PY = 256 / CVB;
@@ -1067,7 +1006,10 @@ extern "C" int dyk_se_pool(const DykEwDesc* d, float* pooled, void* stream) {
         const long hw = (long)d->H * d->W;
         while (HS < DYK_SE_POOL_SPLITS && (long)gx * d->B * HS < 1024 && hw / (HS * 2) >= (long)PY * 8) HS <<= 1;
     }
-    DISPATCH_TF(se_pool_kernel, dim3(gx, d->B, HS), dim3(256), 0, (hipStream_t)stream, *d, pooled, CVB);
+    rc = ew_launch_dtype<true>(d->dtype, [&](auto t) {
+        hipLaunchKernelGGL(se_pool_kernel<ew_t<decltype(t)>>, dim3(gx, d->B, HS), dim3(256), 0, (hipStream_t)stream, *d, pooled, CVB);
+    });
+    if (rc) return rc;
     if (HS > 1) {
         const int n = d->B * d->C;
         hipLaunchKernelGGL(se_pool_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)d->aux2,
@@ -1127,47 +1069,30 @@ extern "C" int dyk_se_fc_bwd(const DykSeFcDesc* d, void* stream) {
 }
 
 extern "C" int dyk_se_scale(const DykEwDesc* d, void* stream) {
-    const int rc = check_ew(d, false);
+    const int rc = ew_check(d, true, false, false, false);
     if (rc) return rc;
     if (!d->p0 || d->B <= 0 || d->H <= 0 || d->W <= 0) return DYK_ERR_ARG;
-    const int CV = d->C / epv_of(d->dtype);
-    int CVB = 1;
-    while (CVB < CV && CVB < 32) CVB <<= 1;
-    const int PY = 256 / CVB, gx = (CV + CVB - 1) / CVB;
-    const long hw = (long)d->H * d->W;
-    long gy = (hw + (long)PY * 8 - 1) / ((long)PY * 8);          // >= 8 pixels per thread
-    const long cap = 4096 / ((long)gx * d->B) > 0 ? 4096 / ((long)gx * d->B) : 1;
-    if (gy > cap) gy = cap;
-    if (gy < 1) gy = 1;
-    dim3 grid(gx, (int)gy, d->B);
+    int gx, gy;
+    const int CVB = ew_grid2d(d->C / ew_epv(d->dtype), (long)d->H * d->W, 4096 / d->B, &gx, &gy);      // at most 4096 workgroups over the B images
+    dim3 grid(gx, gy, d->B);
     if (d->red) {          // with the BatchNorm-backward reduce of the producer of `out`'s tensor (see the kernel)
         if (d->dtype == DYK_F16) return DYK_ERR_UNSUPPORTED;
-        if (!d->b || !d->p2 || d->ldb % epv_of(d->dtype)) return DYK_ERR_ARG;
+        if (!d->b || !d->p2 || d->ldb % ew_epv(d->dtype)) return DYK_ERR_ARG;
         long nz = 768 / ((long)gx * gy);                 // ~3 workgroups per CU, each over B / nz images
         if (nz < 1) nz = 1;
         if (nz > d->B) nz = d->B;
         grid.z = (unsigned)nz;
-#define DYK_SE_RED(A)                                                                                                     \
-        do {                                                                                                              \
-            if (d->dtype == DYK_BF16) hipLaunchKernelGGL((se_scale_kernel<bf16_t, A>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB); \
-            else hipLaunchKernelGGL((se_scale_kernel<float, A>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);        \
-        } while (0)
-        switch (d->act) {
-        case DYK_ACT_MISH: DYK_SE_RED(DYK_ACT_MISH); break;
-        case DYK_ACT_RELU: DYK_SE_RED(DYK_ACT_RELU); break;
-        case DYK_ACT_HSWISH: DYK_SE_RED(DYK_ACT_HSWISH); break;
-        case DYK_ACT_RELU6: DYK_SE_RED(DYK_ACT_RELU6); break;
-        default: DYK_SE_RED(-1); break;
-        }
-#undef DYK_SE_RED
-        DYK_LAUNCH_CHECK();
-        return DYK_OK;
+        // the activations of the layers an SE block follows in the shipped cfgs; any other through the runtime form -1
+        return ew_launch_dtype<false>(d->dtype, [&](auto t) {
+            auto launch = [&](auto A) {
+                hipLaunchKernelGGL((se_scale_kernel<ew_t<decltype(t)>, decltype(A)::value>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
+            };
+            if (!ew_dispatch_int(d->act, EwInts<DYK_ACT_MISH, DYK_ACT_RELU, DYK_ACT_HSWISH, DYK_ACT_RELU6>(), launch)) launch(std::integral_constant<int, -1>());
+        });
     }
-    if (d->dtype == DYK_F16) hipLaunchKernelGGL((se_scale_kernel<f16_t, -2>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    else if (d->dtype == DYK_BF16) hipLaunchKernelGGL((se_scale_kernel<bf16_t, -2>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    else hipLaunchKernelGGL((se_scale_kernel<float, -2>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
-    DYK_LAUNCH_CHECK();
-    return DYK_OK;
+    return ew_launch_dtype<true>(d->dtype, [&](auto t) {
+        hipLaunchKernelGGL((se_scale_kernel<ew_t<decltype(t)>, -2>), grid, dim3(256), 0, (hipStream_t)stream, *d, CVB);
+    });
 }
 
 extern "C" int dyk_head_permute_fwd(const float* y, float* p, int32_t B, int32_t ny, int32_t nx, int32_t na,
@@ -1246,19 +1171,13 @@ extern "C" int dyk_image_prep(const void* src, float* dst, int32_t planes, int32
 extern "C" int dyk_patch_gather(const float* in, void* out, int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t k,
                                 int32_t stride, int32_t pad, int32_t ld, float mul, int32_t dtype, void* stream) {
     if (!in || !out || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || k <= 0 || stride <= 0) return DYK_ERR_ARG;
-    const int epv = epv_of(dtype);
+    const int epv = ew_epv(dtype);
     if (ld % epv || ld < k * k * Cin) return DYK_ERR_ARG;
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     if ((long)B * Ho * Wo >= (1L << 31)) return DYK_ERR_ARG;
     const int grid = ew_grid((long)B * Ho * Wo);
-    if (dtype == DYK_BF16)
-        hipLaunchKernelGGL(patch_gather_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (bf16_t*)out, B, Cin, H, W, k, stride, pad, Ho, Wo, ld, mul);
-    else if (dtype == DYK_F16)
-        hipLaunchKernelGGL(patch_gather_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (f16_t*)out, B, Cin, H, W, k, stride, pad, Ho, Wo, ld, mul);
-    else if (dtype == DYK_F32)
-        hipLaunchKernelGGL(patch_gather_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (float*)out, B, Cin, H, W, k, stride, pad, Ho, Wo, ld, mul);
-    else
-        return DYK_ERR_ARG;
-    DYK_LAUNCH_CHECK();
-    return DYK_OK;
+    return ew_launch_dtype<true>(dtype, [&](auto t) {
+        typedef ew_t<decltype(t)> T;
+        hipLaunchKernelGGL(patch_gather_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, (T*)out, B, Cin, H, W, k, stride, pad, Ho, Wo, ld, mul);
+    });
 }
