@@ -256,6 +256,19 @@ class DykEvalMatchDesc(ctypes.Structure):
                 ("nc", _i32), ("T", _i32), ("rec_cap", _i32)]
 
 
+EVAL_MAX_AREA = 4          # DYK_EVAL_MAX_AREA: area ranges of one dyk_eval_match_coco launch
+EVAL_COCO_MAX_NUM = 512    # DYK_EVAL_COCO_MAX_NUM: detections of one image (the NMS entry points keep at most as many)
+
+
+class DykEvalCocoDesc(ctypes.Structure):
+    _fields_ = [("out", _vp), ("counts", _vp), ("rec_off", _vp), ("targets", _vp), ("gt_off", _vp), ("shape0", _vp),
+                ("unpad", _vp), ("conf", _vp), ("cls", _vp), ("img", _vp), ("rank", _vp), ("box", _vp), ("darea", _vp),
+                ("dtm", _vp), ("dtig", _vp), ("match", _vp), ("err", _vp), ("thr", ctypes.c_double * EVAL_MAX_THR),
+                ("area", (ctypes.c_double * 2) * EVAL_MAX_AREA), ("B", _i32), ("max_num", _i32), ("nt", _i32),
+                ("nc", _i32), ("T", _i32), ("rec_cap", _i32), ("A", _i32), ("max_det", _i32), ("round_boxes", _i32),
+                ("img_base", _i32)]
+
+
 _lib = None
 _P = ctypes.POINTER
 
@@ -349,6 +362,7 @@ SIGNATURES = {
     "dyk_box_convert": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dyk_scale_coords": (_i32, [_vp, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
     "dyk_eval_match": (_i32, [_P(DykEvalMatchDesc), _vp]),
+    "dyk_eval_match_coco": (_i32, [_P(DykEvalCocoDesc), _vp]),
 }
 
 

@@ -1199,6 +1199,68 @@ typedef struct DykEvalMatchDesc {
 } DykEvalMatchDesc;
 int dyk_eval_match(const DykEvalMatchDesc* desc, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * COCO-protocol matching of one evaluation batch (replaces the per-batch half of the training harness's validation,
+ * train_utils/kaist_train_eval_utils.py:122-190: scale_coords + round per image, three device-to-host copies, a dict
+ * per detection, then pycocotools' per-image evaluation).  One launch, one workgroup (a wavefront) per image, no
+ * allocation, no atomics, no synchronisation; the accumulation (once per epoch) stays on the host
+ * (other_utils.metrics.coco_accumulate).  Written from the published algorithm; no COCO tool runs where this project
+ * runs, so agreement with pycocotools is derived (this text, tests/coco_ref.py and its hand cases), not measured.
+ *
+ * Inputs as dyk_eval_match reads them (out, counts, rec_off, targets, gt_off, shape0, unpad), plus area[a] = [lo, hi]
+ * for a < A, max_det, round_boxes, img_base.  Every step is a separate IEEE operation, no FMA:
+ *   ground truth  fp32: gx = (xc - 0.5f*w) * (float)W0, gy = (yc - 0.5f*h) * (float)H0, gw = w * (float)W0,
+ *                 gh = h * (float)H0 (coco_utils.py:33-45 on an fp32 tensor); then exactly to fp64, garea = gw * gh.
+ *   detections    un-letterboxed and clipped with the expressions of dyk_scale_coords when unpad says so; round_boxes
+ *                 != 0: rintf (half to even) on each corner (kaist_train_eval_utils.py:163); dw = x2 - x1, dh = y2 - y1
+ *                 in fp32; then fp64, darea = dw * dh.
+ *   IoU           fp64: w = min(dx+dw, gx+gw) - max(dx, gx), w <= 0 -> 0; h likewise; i = w*h; i / (darea + garea - i).
+ *                 No +1 anywhere.
+ *   rank          within the image and the class value: #{j of the class : s_j > s_i || (s_j == s_i && j < i)} (a stable
+ *                 descending sort); ranks >= max_det take no part in the matching.
+ *   per area a    a ground-truth box is ignored when garea < lo || garea > hi; the boxes of the class are visited
+ *                 non-ignored first, then ignored, each group in row order.
+ *   per (a, t)    detections in rank order: best = min(thr[t], 1 - 1e-10), m = none; walk the boxes in visiting order:
+ *                 skip a box matched at (a, t); stop when m is a non-ignored box and the next one is ignored; skip a box
+ *                 with iou < best; otherwise best = iou, m = this box (on equal IoU the later box wins).  With an m the
+ *                 detection is matched, its ignore flag is m's, and m is matched at (a, t); without one the detection is
+ *                 ignored exactly when darea < lo || darea > hi.
+ * Writes, per detection r = rec_off[b] + i in NMS order: conf[r], cls[r], img[r] = img_base + b, rank[r], box[r][4] (the
+ * corners as used), darea[r], dtm[r][A] / dtig[r][A] (bit t: matched / ignored at (a, t)), match[r][A][T] (index of the
+ * matched box among the image's rows of `targets`, -1 if none).  A detection with rank >= max_det, or with a class outside
+ * [0, nc) (then err[0] = 1), gets zeros in dtm and dtig and -1 in every match.  Tables that leave the arrays, or more than
+ * DYK_EVAL_MAX_GT rows: the image writes nothing and err[1] = 1, as in dyk_eval_match.
+ * DYK_ERR_ARG before any launch: the causes of dyk_eval_match, A outside [1, DYK_EVAL_MAX_AREA], A * T > 64 (one lane
+ * decides one (a, t)), max_det < 1, max_num > DYK_EVAL_COCO_MAX_NUM (the detections of an image are ranked in LDS; the
+ * NMS entry points keep at most that many).
+ * ---------------------------------------------------------------------------------- */
+#define DYK_EVAL_MAX_AREA 4
+#define DYK_EVAL_COCO_MAX_NUM 512
+typedef struct DykEvalCocoDesc {
+    const float* out;
+    const int32_t* counts;
+    const int32_t* rec_off;
+    const float* targets;
+    const int32_t* gt_off;
+    const int32_t* shape0;
+    const float* unpad;
+    float* conf;
+    int32_t* cls;
+    int32_t* img;
+    int32_t* rank;
+    float* box;
+    double* darea;
+    uint32_t* dtm;
+    uint32_t* dtig;
+    int16_t* match;
+    int32_t* err;
+    double thr[DYK_EVAL_MAX_THR];
+    double area[DYK_EVAL_MAX_AREA][2];
+    int32_t B, max_num, nt, nc, T, rec_cap;
+    int32_t A, max_det, round_boxes, img_base;
+} DykEvalCocoDesc;
+int dyk_eval_match_coco(const DykEvalCocoDesc* desc, void* stream);
+
 /* Profiling variant of dyk_run_commands: brackets every command with HIP events on `stream`
  * and, after synchronising the stream, writes each command's duration in milliseconds to
  * ms_out[0..n).  Used by bench.py's roofline pass, never in a timed throughput region. */
