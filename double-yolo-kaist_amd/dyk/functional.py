@@ -2,6 +2,7 @@
 NCHW float32 CUDA tensors (the reference's `module(x)` / `module(x, outputs)` surface).  Each call converts to the
 channels-last compute layout, runs the same HIP kernels the compiled plan uses, and converts back.  This is the
 module-level compatibility surface (no autograd); `models.YOLO.forward` never goes through here.
+The input-side passes on the loader's uint8 batches live here too: prepare_images, clahe, cutout.
 """
 import ctypes
 
@@ -210,3 +211,76 @@ def multi_scale_pair(v_imgs, l_imgs, img_size, gs=32):
     if sf != 1:
         ns = [math.ceil(x * sf / gs) * gs for x in v_imgs.shape[2:]]
     return prepare_images(v_imgs, ns), prepare_images(l_imgs, ns)
+
+
+def _u8_planes(imgs, what):
+    if not isinstance(imgs, torch.Tensor):
+        raise TypeError("%s: a uint8 device tensor [..., H, W], got %s" % (what, type(imgs).__name__))
+    if not imgs.is_cuda:
+        raise TypeError("%s runs on the GPU only (got a %s tensor); there is no CPU fallback" % (what, imgs.device.type))
+    if imgs.dtype != torch.uint8:
+        raise TypeError("%s: uint8 images, got %s" % (what, imgs.dtype))
+    if imgs.dim() < 2:
+        raise ValueError("%s expects [..., H, W], got %s" % (what, tuple(imgs.shape),))
+    if not imgs.is_contiguous():
+        raise ValueError("%s: a contiguous tensor (planar [..., H, W])" % what)
+    H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
+    planes = imgs.numel() // max(H * W, 1)
+    if planes < 1 or H < 1 or W < 1:
+        raise ValueError("%s: an empty tensor %s" % (what, tuple(imgs.shape),))
+    return planes, H, W
+
+
+def clahe(imgs, clip_limit=1.0, tile_grid_size=(4, 4), out=None):
+    """OpenCV's 8-bit CLAHE (cv2.createCLAHE(clipLimit, tileGridSize).apply) on every plane of a uint8 device tensor
+    [..., H, W], e.g. the loader's [B,3,H,W]: dyk_clahe, two launches, no synchronisation; the rule is in include/dyk_hip.h.
+    `tile_grid_size` is (tiles_x, tiles_y) as in cv2; `out` may be `imgs` itself.  ValueError for what the rule refuses:
+    a grid outside 1..16, a pad beyond n - 1 pixels on its axis, a tile above 2^24 pixels."""
+    planes, H, W = _u8_planes(imgs, "clahe")
+    try:
+        tx, ty = (int(t) for t in tile_grid_size)
+    except (TypeError, ValueError):
+        raise TypeError("clahe: tile_grid_size is (tiles_x, tiles_y), got %r" % (tile_grid_size,))
+    if not (1 <= tx <= L.CLAHE_MAX_TILES and 1 <= ty <= L.CLAHE_MAX_TILES):
+        raise ValueError("clahe: tile_grid_size within 1..%d per axis, got %r" % (L.CLAHE_MAX_TILES, tile_grid_size))
+    padx, pady = (0, 0) if (W % tx == 0 and H % ty == 0) else (tx - W % tx, ty - H % ty)
+    if padx > W - 1 or pady > H - 1:
+        raise ValueError("clahe: a %dx%d image cannot be padded by (%d, %d) for a %r grid" % (H, W, pady, padx, tile_grid_size))
+    if ((W + padx) // tx) * ((H + pady) // ty) > 1 << 24:
+        raise ValueError("clahe: tiles of more than 2^24 pixels")
+    if out is None:
+        out = torch.empty_like(imgs)
+    elif _u8_planes(out, "clahe(out=)") != (planes, H, W) or out.shape != imgs.shape or out.device != imgs.device:
+        raise ValueError("clahe: out must match imgs, got %s for %s" % (tuple(out.shape), tuple(imgs.shape)))
+    lut = torch.empty(load().dyk_clahe_ws_bytes(planes, tx, ty), dtype=torch.uint8, device=imgs.device)
+    d = L.DykClaheDesc(src=imgs.data_ptr(), dst=out.data_ptr(), lut=lut.data_ptr(), planes=planes, H=H, W=W, tiles_x=tx,
+                       tiles_y=ty, clip_limit=float(clip_limit))
+    check(load().dyk_clahe(ctypes.byref(d), _stream()), "dyk_clahe")
+    return out
+
+
+def cutout(imgs, rects, value=0):
+    """Set rectangles of a uint8 device tensor [..., C, H, W] to `value`, in place, in one launch (dyk_cutout_rects; the
+    cut-outs of build_utils.snowflake).  `rects` int32 (xmin, ymin, xmax, ymax), upper ends exclusive, clipped to the image:
+    [nrect,4] for every plane, or [B,nrect,4] with B = imgs.shape[0], one set per image.  A host `rects` goes up in one
+    small copy; nothing synchronises."""
+    planes, H, W = _u8_planes(imgs, "cutout")
+    if not isinstance(rects, torch.Tensor):
+        raise TypeError("cutout: rects is an int32 tensor, got %s" % type(rects).__name__)
+    if rects.dtype != torch.int32:
+        raise TypeError("cutout: int32 rects, got %s" % rects.dtype)
+    if rects.dim() == 2 and rects.shape[1] == 4:
+        nsets = 1
+    elif rects.dim() == 3 and rects.shape[2] == 4 and imgs.dim() >= 3 and rects.shape[0] == imgs.shape[0]:
+        nsets = int(rects.shape[0])
+    else:
+        raise ValueError("cutout: rects [nrect,4] or [%s,nrect,4], got %s" % (imgs.shape[0] if imgs.dim() else "B", tuple(rects.shape)))
+    if not 0 <= int(value) <= 255:
+        raise ValueError("cutout: value within 0..255, got %r" % (value,))
+    nrect = int(rects.shape[-2])
+    if nrect == 0:
+        return imgs
+    rects = rects.contiguous().to(imgs.device, non_blocking=True)
+    check(load().dyk_cutout_rects(imgs.data_ptr(), planes, H, W, rects.data_ptr(), nrect, planes // nsets, int(value), _stream()),
+          "dyk_cutout_rects")
+    return imgs

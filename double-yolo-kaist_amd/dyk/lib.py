@@ -269,6 +269,14 @@ class DykEvalCocoDesc(ctypes.Structure):
                 ("img_base", _i32)]
 
 
+CLAHE_MAX_TILES = 16       # tiles per axis of dyk_clahe (include/dyk_hip.h)
+
+
+class DykClaheDesc(ctypes.Structure):
+    _fields_ = [("src", _vp), ("dst", _vp), ("lut", _vp), ("planes", _i32), ("H", _i32), ("W", _i32), ("tiles_x", _i32),
+                ("tiles_y", _i32), ("clip_limit", ctypes.c_double)]
+
+
 _lib = None
 _P = ctypes.POINTER
 
@@ -363,6 +371,9 @@ SIGNATURES = {
     "dyk_scale_coords": (_i32, [_vp, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
     "dyk_eval_match": (_i32, [_P(DykEvalMatchDesc), _vp]),
     "dyk_eval_match_coco": (_i32, [_P(DykEvalCocoDesc), _vp]),
+    "dyk_clahe_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "dyk_clahe": (_i32, [_P(DykClaheDesc), _vp]),
+    "dyk_cutout_rects": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
 }
 
 

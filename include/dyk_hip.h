@@ -1261,6 +1261,60 @@ typedef struct DykEvalCocoDesc {
 } DykEvalCocoDesc;
 int dyk_eval_match_coco(const DykEvalCocoDesc* desc, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The "snowflake" input transform on the device (reference build_utils/snowflake.py: contrast-limited adaptive histogram
+ * equalisation of every channel of both streams, then square cut-outs): dyk_clahe and dyk_cutout_rects.
+ *
+ * dyk_clahe is OpenCV's 8-bit CLAHE (modules/imgproc/src/clahe.cpp), per plane of src[planes][H][W].  Written from the
+ * published algorithm; no OpenCV runs where this project runs, so agreement with it is derived (this text,
+ * tests/clahe_ref.py and its hand cases), not measured.  The rule:
+ *   geometry      W % tiles_x == 0 && H % tiles_y == 0: padx = pady = 0.  Otherwise padx = tiles_x - W % tiles_x and
+ *                 pady = tiles_y - H % tiles_y -- a divisible axis then gets a full extra tiles_x / tiles_y (OpenCV does so).
+ *                 The tiles cover the image extended by BORDER_REFLECT_101 (index j >= n reads 2(n-1) - j), read through
+ *                 the index map, never materialised.  tw = (W+padx)/tiles_x, th = (H+pady)/tiles_y, area = tw*th.
+ *   constants     lutScale = 255.0f / (float)area in fp32;
+ *                 clip = clip_limit > 0 ? max((int)(clip_limit * area / 256), 1) : 0, product and quotient in double.
+ *   per tile      1. the 256-bin int histogram of its tw x th extended pixels;
+ *                 2. if clip > 0: clipped = sum(max(h - clip, 0)), every bin becomes min(h, clip); batch = clipped / 256,
+ *                    residual = clipped - 256*batch; every bin += batch; if residual != 0: step = max(256 / residual, 1) and
+ *                    the bins 0, step, 2*step, ... get +1 each while the index is < 256 and fewer than `residual` bins
+ *                    have been incremented;
+ *                 3. lut[i] = saturate_u8(rint_half_even((float)prefix_sum_i * lutScale)), prefix sum inclusive.
+ *   per pixel     (y, x) of the original H x W, v = src: txf = x * (1.0f/tw) - 0.5f, tx1 = floor(txf), xa = txf - tx1,
+ *                 xa1 = 1.0f - xa; then tx1 is clamped at 0 and tx2 = tx1 + 1 (of the unclamped tx1) at tiles_x - 1 -- the
+ *                 clamping comes after xa is formed; the same in y.  With L[ty][tx] the table of tile (ty, tx):
+ *                 res = (L[ty1][tx1][v]*xa1 + L[ty1][tx2][v]*xa)*ya1 + (L[ty2][tx1][v]*xa1 + L[ty2][tx2][v]*xa)*ya,
+ *                 dst = saturate_u8(rint_half_even(res)).
+ *   fp32          every multiply, add and subtract above is an IEEE fp32 operation rounded on its own, in exactly this
+ *                 order, no FMA: plain numpy reproduces the output bit for bit.
+ * Two launches on `stream` (tables, then pixels), no allocation, no synchronisation.  `lut` is the workspace
+ * [planes][tiles_y*tiles_x][256] of dyk_clahe_ws_bytes(planes, tiles_x, tiles_y) = planes*tiles_x*tiles_y*256 bytes (a
+ * negative DYK_ERR_ARG for planes < 1 or a grid outside 1..16); it holds the tables afterwards.  dst == src is allowed: a
+ * pixel reads only its own source byte.  Any alignment works; 4-byte aligned src / dst with W % 4 == 0 and a 16-byte
+ * aligned lut take the vector paths.
+ * DYK_ERR_ARG before any launch: a null pointer; planes, H or W < 1; tiles_x / tiles_y outside 1..16; a pad larger than
+ * n - 1 on its axis (the reflection is undefined); area > 2^24 (above it (float)prefix_sum stops being exact);
+ * planes * max(H, 256) > INT32_MAX (one grid dimension).
+ *
+ * dyk_cutout_rects: plane p of img[planes][H][W] uses the rectangle set p / planes_per_set of
+ * rects[nsets][nrect][4] = (xmin, ymin, xmax, ymax), in device memory; rows [ymin, ymax) and columns [xmin, xmax) are set to
+ * `value` -- the upper ends are exclusive, as in the reference's slices (snowflake.py:88-91).  Rectangles are clipped to the
+ * image; empty or inverted ones write nothing.  One launch for all planes; nrect == 0 launches nothing.
+ * DYK_ERR_ARG: null img, null rects with nrect > 0, planes / H / W / planes_per_set < 1, nrect < 0, value outside 0..255,
+ * H*W or planes*nrect > INT32_MAX.
+ * ---------------------------------------------------------------------------------- */
+typedef struct DykClaheDesc {
+    const uint8_t* src;   /* [planes][H][W] */
+    uint8_t* dst;         /* [planes][H][W]; dst == src allowed */
+    uint8_t* lut;         /* workspace [planes][tiles_y*tiles_x][256] */
+    int32_t planes, H, W, tiles_x, tiles_y;
+    double clip_limit;    /* <= 0: no clipping */
+} DykClaheDesc;
+int64_t dyk_clahe_ws_bytes(int32_t planes, int32_t tiles_x, int32_t tiles_y);
+int dyk_clahe(const DykClaheDesc* desc, void* stream);
+int dyk_cutout_rects(uint8_t* img, int32_t planes, int32_t H, int32_t W, const int32_t* rects, int32_t nrect,
+                     int32_t planes_per_set, int32_t value, void* stream);
+
 /* Profiling variant of dyk_run_commands: brackets every command with HIP events on `stream`
  * and, after synchronising the stream, writes each command's duration in milliseconds to
  * ms_out[0..n).  Used by bench.py's roofline pass, never in a timed throughput region. */
