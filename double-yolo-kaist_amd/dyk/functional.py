@@ -2,7 +2,7 @@
 NCHW float32 CUDA tensors (the reference's `module(x)` / `module(x, outputs)` surface).  Each call converts to the
 channels-last compute layout, runs the same HIP kernels the compiled plan uses, and converts back.  This is the
 module-level compatibility surface (no autograd); `models.YOLO.forward` never goes through here.
-The input-side passes on the loader's uint8 batches live here too: prepare_images, clahe, cutout.
+The input-side passes on the loader's uint8 batches live here too: prepare_images, clahe, cutout, augment_pairs.
 """
 import ctypes
 
@@ -284,3 +284,162 @@ def cutout(imgs, rects, value=0):
     check(load().dyk_cutout_rects(imgs.data_ptr(), planes, H, W, rects.data_ptr(), nrect, planes // nsets, int(value), _stream()),
           "dyk_cutout_rects")
     return imgs
+
+
+def invert_affine(M):
+    """The inverse of a forward affine matrix (rows 0 and 1 of a 2 x 3 or 3 x 3) as dyk_augment_pairs takes it: six Python
+    floats, formed in fp64 in exactly the order of the rule (include/dyk_hip.h, (b)).  ValueError for a non-finite or
+    singular matrix."""
+    import math
+    m = [float(M[0][0]), float(M[0][1]), float(M[0][2]), float(M[1][0]), float(M[1][1]), float(M[1][2])]
+    if not all(math.isfinite(t) for t in m):
+        raise ValueError("augment_pairs: a non-finite matrix %r" % (m,))
+    D = m[0] * m[4] - m[1] * m[3]
+    if D == 0.0:
+        raise ValueError("augment_pairs: a singular matrix %r" % (m,))
+    D = 1.0 / D
+    A11 = m[4] * D
+    A22 = m[0] * D
+    m[0] = A11
+    m[1] *= -D
+    m[3] *= -D
+    m[4] = A22
+    b1 = -m[0] * m[2] - m[1] * m[5]
+    b2 = -m[3] * m[2] - m[4] * m[5]
+    m[2] = b1
+    m[5] = b2
+    if not all(math.isfinite(t) for t in m):
+        raise ValueError("augment_pairs: the inverse of the matrix is not finite: %r" % (m,))
+    return m
+
+
+def _host_array(a, dtype, shape, what):
+    import numpy as np
+    if isinstance(a, torch.Tensor):
+        if a.is_cuda:
+            raise TypeError("augment_pairs: %s is a host array (it goes up with the other parameters in one copy)" % what)
+        a = a.numpy()
+    a = np.asarray(a)
+    if dtype == np.uint8 and a.dtype not in (np.uint8, np.bool_):
+        raise TypeError("augment_pairs: %s is uint8, got %s" % (what, a.dtype))
+    if dtype == np.int32 and a.dtype.kind not in "iu":
+        raise TypeError("augment_pairs: %s holds integers, got %s" % (what, a.dtype))
+    if a.ndim != len(shape) or any(s is not None and s != t for s, t in zip(shape, a.shape)):
+        raise ValueError("augment_pairs: %s has shape %s, got %s" % (what, ["B" if s is None else s for s in shape], a.shape))
+    return np.ascontiguousarray(a.astype(dtype, copy=False))
+
+
+def augment_pairs(v, l, matrices=None, rects=None, canvas=None, out_size=None, luts=None, flip=None, out=None):
+    """Mosaic canvas, affine warp, HSV jitter and left-right flip of image pairs in ONE launch (dyk_augment_pairs,
+    csrc/augment.hip; the rule is in include/dyk_hip.h).  `v`, `l`: uint8 device batches [N,3,H,W].  All of the following are
+    host arrays, per output image b of B, shared by both streams, and go up in one small copy from pinned memory; nothing
+    synchronises:
+      matrices [B,2,3] fp64   the FORWARD matrix (source -> output), as cv2.warpAffine takes it; inverted here.  None: identity
+      rects    [B,4,8] int32  (x1, y1, x2, y2, src, dx, dy, 0) with canvas=(Hc, Wc): the virtual canvas.  None: image b itself
+      out_size (Ho, Wo)       default: the canvas size
+      luts     [B,3,256] u8   the hue / saturation / value tables.  None: no jitter
+      flip     [B]            non-zero: store mirrored.  None: none
+    `out=(ov, ol)`: uint8 [B,3,Ho,Wo]; they may be `v`, `l` themselves only for jitter alone.  -> (ov, ol).
+    TypeError / ValueError for what the entry refuses and for the warp limits: a non-finite or singular matrix, a size above
+    16384, a matrix that maps an output corner to 2^20 pixels or beyond or moves the source that far across the output, a
+    rectangle that reaches outside its source."""
+    import numpy as np
+    for t, what in ((v, "v"), (l, "l")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("augment_pairs: %s is a uint8 device tensor [N,3,H,W], got %s" % (what, type(t).__name__))
+        if not t.is_cuda:
+            raise TypeError("augment_pairs runs on the GPU only (got a %s tensor); there is no CPU fallback" % t.device.type)
+        if t.dtype != torch.uint8:
+            raise TypeError("augment_pairs: uint8 images, got %s" % t.dtype)
+        if t.dim() != 4 or t.shape[1] != 3 or not t.is_contiguous() or t.numel() == 0:
+            raise ValueError("augment_pairs: %s is a contiguous planar batch [N,3,H,W], got %s" % (what, tuple(t.shape)))
+    if v.shape != l.shape or v.device != l.device:
+        raise ValueError("augment_pairs: two batches of one shape on one device, got %s and %s" % (tuple(v.shape), tuple(l.shape)))
+    N, _, H, W = (int(s) for s in v.shape)
+    B = None
+    for a in (matrices, rects, luts, flip):
+        if a is not None:
+            B = len(a)
+            break
+    B = N if B is None else B
+    if B < 1:
+        raise ValueError("augment_pairs: an empty batch of parameters")
+    if rects is None:
+        if canvas is not None and tuple(canvas) != (H, W):
+            raise ValueError("augment_pairs: canvas= belongs to rects=; without them the canvas is the image, %r" % ((H, W),))
+        if B != N:
+            raise ValueError("augment_pairs: %d parameter sets for %d images; only rects= can pick sources" % (B, N))
+        Hc, Wc = H, W
+    else:
+        if canvas is None:
+            raise ValueError("augment_pairs: rects= needs canvas=(Hc, Wc)")
+        Hc, Wc = (int(s) for s in canvas)
+    Ho, Wo = (Hc, Wc) if out_size is None else (int(s) for s in out_size)
+    sizes = (N, B, H, W, Hc, Wc, Ho, Wo)
+    if min(sizes) < 1 or max(sizes) > L.AUGMENT_MAX_SIZE:
+        raise ValueError("augment_pairs: every size within 1..%d, got N, B, H, W, Hc, Wc, Ho, Wo = %r" % (L.AUGMENT_MAX_SIZE, sizes))
+    if matrices is None and (Ho, Wo) != (Hc, Wc):
+        raise ValueError("augment_pairs: out_size %r differs from the canvas %r and there is no matrix" % ((Ho, Wo), (Hc, Wc)))
+
+    parts, offs, nbytes = {}, {}, 0
+    if matrices is not None:
+        M = _host_array(matrices, np.float64, (B, 2, 3), "matrices")
+        minv = np.empty((B, 6), np.float64)
+        for b in range(B):
+            m = minv[b] = invert_affine(M[b])
+            for x, y in ((0, 0), (Wo - 1, 0), (0, Ho - 1), (Wo - 1, Ho - 1)):
+                if not (abs(m[0] * x + m[1] * y + m[2]) < 2.0 ** 20 and abs(m[3] * x + m[4] * y + m[5]) < 2.0 ** 20):
+                    raise ValueError("augment_pairs: matrix %d maps the output corner (%d, %d) 2^20 pixels away or more" % (b, x, y))
+            # the column and row terms on their own (ad, bd, X0, Y0 of the rule): with these below 2^20 no rn saturates
+            if not max(abs(m[0] * (Wo - 1)), abs(m[3] * (Wo - 1)), abs(m[1] * (Ho - 1)), abs(m[4] * (Ho - 1))) < 2.0 ** 20:
+                raise ValueError("augment_pairs: matrix %d moves the source by 2^20 pixels or more across the output" % b)
+        parts["minv"] = minv
+    if rects is not None:
+        R = _host_array(rects, np.int32, (B, 4, 8), "rects")
+        for b in range(B):
+            for x1, y1, x2, y2, s, dx, dy, _pad in R[b].tolist():
+                x1, y1, x2, y2 = max(x1, 0), max(y1, 0), min(x2, Wc), min(y2, Hc)
+                if x2 <= x1 or y2 <= y1:
+                    continue                                     # an unused slot
+                if not (0 <= s < N and x1 - dx >= 0 and x2 - dx <= W and y1 - dy >= 0 and y2 - dy <= H):
+                    raise ValueError("augment_pairs: rectangle %r of image %d reaches outside source %d of %d x %d"
+                                     % ((x1, y1, x2, y2, dx, dy), b, s, H, W))
+        parts["rects"] = R
+    if luts is not None:
+        parts["luts"] = _host_array(luts, np.uint8, (B, 3, 256), "luts")
+    if flip is not None:
+        parts["flip"] = _host_array(np.asarray(flip.numpy() if isinstance(flip, torch.Tensor) else flip).astype(bool), np.uint8, (B,), "flip")
+
+    if out is None:
+        ov = torch.empty((B, 3, Ho, Wo), dtype=torch.uint8, device=v.device)
+        ol = torch.empty_like(ov)
+    else:
+        ov, ol = out
+        for t in (ov, ol):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != v.device:
+                raise TypeError("augment_pairs: out=(ov, ol), uint8 tensors on the device of the images")
+            if tuple(t.shape) != (B, 3, Ho, Wo) or not t.is_contiguous():
+                raise ValueError("augment_pairs: out tensors are contiguous %r, got %s" % ((B, 3, Ho, Wo), tuple(t.shape)))
+
+    ptr = dict.fromkeys(("minv", "rects", "luts", "flip"))
+    if parts:
+        for k in ("minv", "rects", "luts", "flip"):              # fp64 first, then int32, then bytes: every part aligned
+            if k in parts:
+                offs[k] = nbytes
+                nbytes += parts[k].nbytes
+        host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        hv = host.numpy()
+        for k, o in offs.items():
+            hv[o:o + parts[k].nbytes] = parts[k].reshape(-1).view(np.uint8)
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=v.device)
+        dev.copy_(host, non_blocking=True)
+        for k, o in offs.items():
+            ptr[k] = dev.data_ptr() + o
+    d = L.DykAugmentDesc(src_v=v.data_ptr(), src_l=l.data_ptr(), dst_v=ov.data_ptr(), dst_l=ol.data_ptr(), N=N, B=B, H=H, W=W,
+                         Hc=Hc, Wc=Wc, Ho=Ho, Wo=Wo, rects=ptr["rects"], minv=ptr["minv"], luts=ptr["luts"], flip=ptr["flip"])
+    rc = load().dyk_augment_pairs(ctypes.byref(d), _stream())
+    if rc == -1:
+        raise ValueError("augment_pairs: dyk_augment_pairs refused the call (out tensors that overlap the inputs, or each other? "
+                         "only jitter alone may run in place)")
+    check(rc, "dyk_augment_pairs")
+    return ov, ol

@@ -277,6 +277,14 @@ class DykClaheDesc(ctypes.Structure):
                 ("tiles_y", _i32), ("clip_limit", ctypes.c_double)]
 
 
+AUGMENT_MAX_SIZE = 16384   # every size of dyk_augment_pairs (include/dyk_hip.h)
+
+
+class DykAugmentDesc(ctypes.Structure):
+    _fields_ = [("src_v", _vp), ("src_l", _vp), ("dst_v", _vp), ("dst_l", _vp), ("N", _i32), ("B", _i32), ("H", _i32), ("W", _i32),
+                ("Hc", _i32), ("Wc", _i32), ("Ho", _i32), ("Wo", _i32), ("rects", _vp), ("minv", _vp), ("luts", _vp), ("flip", _vp)]
+
+
 _lib = None
 _P = ctypes.POINTER
 
@@ -374,6 +382,8 @@ SIGNATURES = {
     "dyk_clahe_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "dyk_clahe": (_i32, [_P(DykClaheDesc), _vp]),
     "dyk_cutout_rects": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "dyk_augment_pairs": (_i32, [_P(DykAugmentDesc), _vp]),
+    "dyk_augment_pairs_rows": (_i32, [_P(DykAugmentDesc), _i32, _vp]),
 }
 
 

@@ -1315,6 +1315,74 @@ int dyk_clahe(const DykClaheDesc* desc, void* stream);
 int dyk_cutout_rects(uint8_t* img, int32_t planes, int32_t H, int32_t W, const int32_t* rects, int32_t nrect,
                      int32_t planes_per_set, int32_t value, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The random training augmentation of image pairs on the device (reference build_utils/kaist_dataset.py:213-286 mosaic,
+ * :408-479 random_affine, :482-506 augment_hsv, :362-369 flip): dyk_augment_pairs, ONE launch for both streams of a batch.
+ * The draws and the label arithmetic stay on the host (build_utils/augment.py); every pixel is made here.
+ *
+ * The rule is the classical OpenCV 8-bit path -- warpAffine(INTER_LINEAR, BORDER_CONSTANT 0), then cvtColor BGR2HSV, three
+ * table look-ups, cvtColor HSV2BGR -- written down as this project's own rule.  It is DERIVED, NOT MEASURED: no OpenCV runs
+ * where this project runs, and newer OpenCV releases changed their warp kernels; what is held bit for bit is this text,
+ * tests/augment_ref.py and its hand-worked cases.  Per output pixel the stages run in the order warp, HSV, flipped store.
+ *
+ * (a) Virtual canvas.  Output image b samples a canvas of Hc x Wc pixels made of up to four disjoint rectangles, int32
+ *     records rects[b][4][8] = (x1, y1, x2, y2, src, dx, dy, pad), upper ends exclusive:
+ *         canvas(b, c, y, x) = src_img[src][c][y - dy][x - dx]   when (x, y) lies inside a rectangle (the first that holds it),
+ *                              0                                  everywhere else, outside the canvas included.
+ *     The mosaic's background and the warp's border value are both 0: one rule.  A rectangle is clipped to the canvas; one
+ *     that is empty, names a src outside 0..N-1 or reaches outside its source image is skipped whole (the kernel never reads
+ *     outside src; the Python wrapper refuses such rectangles).  rects == NULL: the one rectangle (0, 0, W, H, b, 0, 0) on a
+ *     canvas of H x W.
+ * (b) Warp.  minv[b][6] is the INVERSE map (output -> canvas), fp64.  The host inverts the forward matrix M (2 x 3) in fp64 in
+ *     exactly this order: D = M0*M4 - M1*M3; D = 1/D; A11 = M4*D; A22 = M0*D; M0 = A11; M1 *= -D; M3 *= -D; M4 = A22;
+ *     b1 = -M0*M2 - M1*M5; b2 = -M3*M2 - M4*M5; M2 = b1; M5 = b2.   rn = round half to even to int32, saturating.
+ *         per output column x:   ad = rn(m0*x*1024),                 bd = rn(m3*x*1024)
+ *         per output row y:      X0 = rn((m1*y + m2)*1024) + 16,     Y0 = rn((m4*y + m5)*1024) + 16
+ *     every fp64 multiply and add rounded on its own (no fused multiply-add).  Then, with arithmetic shifts on negatives,
+ *         X = (X0 + ad) >> 5;  Y = (Y0 + bd) >> 5;  sx = X >> 5;  sy = Y >> 5;  fx = X & 31;  fy = Y & 31
+ *         acc = (32-fx)(32-fy)*c(sy,sx) + fx(32-fy)*c(sy,sx+1) + (32-fx)fy*c(sy+1,sx) + fx*fy*c(sy+1,sx+1)
+ *         out = (acc + 512) >> 10
+ *     with each tap c(y, x) = canvas(b, c, y, x) on its own: taps may straddle a seam or the border.  minv == NULL: identity
+ *     (out = canvas at the same pixel).  The Python wrapper admits only finite, non-singular matrices, sizes up to 16384 and
+ *     maps whose output corners, and whose column and row terms m0*(Wo-1), m3*(Wo-1), m1*(Ho-1), m4*(Ho-1), all stay below
+ *     2^20 pixels in magnitude, so no rn saturates in an admitted call.  (The C entry itself admits any matrix: rn saturates
+ *     and the two sums wrap as unsigned, and the canvas look-up bounds every tap.)
+ * (c) HSV jitter.  Planes are R, G, B.  v = max, vmin = min, diff = v - vmin;
+ *         s = (diff * sdiv[v] + 2048) >> 12
+ *         h = (g - b) if v == r, else (b - r + 2 diff) if v == g, else (r - g + 4 diff)
+ *         h = (h * hdiv[diff] + 2048) >> 12;  if h < 0: h += 180
+ *     sdiv[i] = rn((255 << 12) / (1.0 * i)), hdiv[i] = rn((180 << 12) / (6.0 * i)) in fp64, entry 0 of each 0.  Then
+ *     (h, s, v) = (luts[b][0][h], luts[b][1][s], luts[b][2][v]) and back to RGB in fp32, every operation rounded on its own:
+ *         hf = h*(6.f/180.f); sf = s*(1.f/255.f); vf = v*(1.f/255.f); sector = floor(hf) (0..5 for h <= 179); f = hf - sector
+ *         tab = {vf, vf*(1-sf), vf*(1-sf*f), vf*(1-sf*(1-f))}
+ *         (b, g, r) = tab[{{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}}[sector]];   r = g = b = vf when s == 0
+ *         channel = clip(rint_half_even(x * 255.f), 0, 255)
+ *     A table hue above 179 is taken as sector 5 (the tables of build_utils.augment never hold one).  luts == NULL: no jitter.
+ * (d) Flip.  flip[b] != 0: the pixel computed for column x is stored at column Wo-1-x.  flip == NULL: none.
+ *
+ * Both streams of image b share matrix, rectangles, table and flip.  rects / minv / luts / flip are DEVICE pointers (the
+ * wrapper sends them up in one small copy from pinned memory); no allocation, no synchronisation, no atomics.
+ * DYK_ERR_ARG before the launch: a null descriptor or image pointer; N, B, H, W, Ho, Wo < 1 (Hc, Wc too when rects is given)
+ * or any size above 16384; rects == NULL with B > N; minv == NULL with (Ho, Wo) != the canvas size (H, W without rects);
+ * a dst range that overlaps a src range or the other dst -- except dst_v == src_v and dst_l == src_l exactly with minv, rects
+ * and flip all NULL and B == N (jitter alone may run in place: a pixel reads only its own three bytes).
+ * ---------------------------------------------------------------------------------- */
+typedef struct DykAugmentDesc {
+    const uint8_t* src_v;   /* [N][3][H][W] */
+    const uint8_t* src_l;   /* [N][3][H][W] */
+    uint8_t* dst_v;         /* [B][3][Ho][Wo] */
+    uint8_t* dst_l;         /* [B][3][Ho][Wo] */
+    int32_t N, B, H, W, Hc, Wc, Ho, Wo;
+    const int32_t* rects;   /* [B][4][8] or NULL */
+    const double* minv;     /* [B][6] or NULL */
+    const uint8_t* luts;    /* [B][3][256] or NULL */
+    const uint8_t* flip;    /* [B] or NULL */
+} DykAugmentDesc;
+int dyk_augment_pairs(const DykAugmentDesc* desc, void* stream);
+/* The same launch with `rows` (1..64) output rows per workgroup instead of the built-in choice: for tools/augment_probe.py,
+ * which measures that choice; the output does not depend on it.  DYK_ERR_ARG for rows outside 1..64. */
+int dyk_augment_pairs_rows(const DykAugmentDesc* desc, int32_t rows, void* stream);
+
 /* Profiling variant of dyk_run_commands: brackets every command with HIP events on `stream`
  * and, after synchronising the stream, writes each command's duration in milliseconds to
  * ms_out[0..n).  Used by bench.py's roofline pass, never in a timed throughput region. */
