@@ -2,7 +2,8 @@
 NCHW float32 CUDA tensors (the reference's `module(x)` / `module(x, outputs)` surface).  Each call converts to the
 channels-last compute layout, runs the same HIP kernels the compiled plan uses, and converts back.  This is the
 module-level compatibility surface (no autograd); `models.YOLO.forward` never goes through here.
-The input-side passes on the loader's uint8 batches live here too: prepare_images, clahe, cutout, augment_pairs.
+The input-side passes on the loader's uint8 batches live here too: prepare_images, clahe, cutout, augment_pairs,
+resize_pad_pairs.
 """
 import ctypes
 
@@ -442,4 +443,90 @@ def augment_pairs(v, l, matrices=None, rects=None, canvas=None, out_size=None, l
         raise ValueError("augment_pairs: dyk_augment_pairs refused the call (out tensors that overlap the inputs, or each other? "
                          "only jitter alone may run in place)")
     check(rc, "dyk_augment_pairs")
+    return ov, ol
+
+
+RESIZE_LINEAR, RESIZE_AREA = 0, 1
+_LAYOUTS = {"chw": 0, "hwc_bgr": 1}
+
+
+def _image_list(t, what, layout):
+    """a batch tensor or a list of per-image tensors -> [(tensor, h, w)], every one a contiguous uint8 device image"""
+    imgs = list(t.unbind(0)) if isinstance(t, torch.Tensor) else list(t)
+    out = []
+    for i, im in enumerate(imgs):
+        if not isinstance(im, torch.Tensor):
+            raise TypeError("resize_pad_pairs: %s[%d] is a uint8 device tensor, got %s" % (what, i, type(im).__name__))
+        if not im.is_cuda:
+            raise TypeError("resize_pad_pairs runs on the GPU only (%s[%d] is a %s tensor); there is no CPU fallback" % (what, i, im.device.type))
+        if im.dtype != torch.uint8:
+            raise TypeError("resize_pad_pairs: uint8 images, got %s for %s[%d]" % (im.dtype, what, i))
+        ch = 0 if layout == "chw" else 2
+        if im.dim() != 3 or im.shape[ch] != 3 or not im.is_contiguous() or im.numel() == 0:
+            raise ValueError("resize_pad_pairs: %s[%d] is a contiguous %s image, got %s" % (what, i, "[3,h,w]" if layout == "chw" else "[h,w,3]", tuple(im.shape)))
+        h, w = (int(im.shape[1]), int(im.shape[2])) if layout == "chw" else (int(im.shape[0]), int(im.shape[1]))
+        out.append((im, h, w))
+    return out
+
+
+def resize_pad_pairs(v_list, l_list, geom, out_size, layout="chw", color=(0, 0, 0), out=None):
+    """Resize (LINEAR / AREA) and letterbox of image pairs in ONE launch (dyk_resize_pad_pairs, csrc/letterbox.hip; the rule is
+    in include/dyk_hip.h).  `v_list`, `l_list`: a uint8 device batch [B,3,h,w] (layout "chw") or [B,h,w,3] (layout "hwc_bgr":
+    cv2.imread's array, the channels reversed on the way so that the output is planar RGB), or lists of B per-image tensors,
+    which may differ in size from image to image (not between the two streams).  `geom`: per image (nh, nw, top, left, interp)
+    on the host -- the resized content size, its place in the output, RESIZE_LINEAR (0) or RESIZE_AREA (1); both streams share
+    it.  `out_size` (Ho, Wo); `color` the border value per output plane; `out=(ov, ol)` uint8 [B,3,Ho,Wo].  The records and
+    source addresses go up in one small copy from pinned memory; nothing synchronises.  -> (ov, ol).
+    TypeError / ValueError for everything the entry refuses (sizes outside 1..16384, a content rectangle outside the output, AREA
+    that would enlarge, overlapping tensors) and for non-uint8, non-contiguous or host tensors."""
+    import numpy as np
+    if layout not in _LAYOUTS:
+        raise ValueError("resize_pad_pairs: layout is 'chw' or 'hwc_bgr', got %r" % (layout,))
+    vs, ls = _image_list(v_list, "v_list", layout), _image_list(l_list, "l_list", layout)
+    B = len(vs)
+    if B < 1 or len(ls) != B or len(geom) != B:
+        raise ValueError("resize_pad_pairs: %d visible images, %d LWIR images and %d geometry records" % (B, len(ls), len(geom)))
+    Ho, Wo = (int(s) for s in out_size)
+    color = [int(c) for c in (color if hasattr(color, "__len__") else (color,) * 3)]
+    if len(color) != 3 or min(color) < 0 or max(color) > 255:
+        raise ValueError("resize_pad_pairs: color is three values of 0..255, got %r" % (color,))
+    M = L.RESIZE_PAD_MAX_SIZE
+    if not (1 <= B <= M and 1 <= Ho <= M and 1 <= Wo <= M):
+        raise ValueError("resize_pad_pairs: B, Ho, Wo within 1..%d, got %r" % (M, (B, Ho, Wo)))
+    dev = vs[0][0].device
+    recs = (L.DykResizePadRec * B)()
+    for b, ((v, h, w), (l, hl, wl)) in enumerate(zip(vs, ls)):
+        if (h, w) != (hl, wl) or v.device != dev or l.device != dev:
+            raise ValueError("resize_pad_pairs: image %d: the two streams have one size and one device, got %s and %s" % (b, tuple(v.shape), tuple(l.shape)))
+        nh, nw, top, left, interp = (int(t) for t in geom[b])
+        if not (1 <= h <= M and 1 <= w <= M and 1 <= nh <= M and 1 <= nw <= M):
+            raise ValueError("resize_pad_pairs: image %d: sizes within 1..%d, got %r -> %r" % (b, M, (h, w), (nh, nw)))
+        if interp not in (RESIZE_LINEAR, RESIZE_AREA):
+            raise ValueError("resize_pad_pairs: image %d: interp is RESIZE_LINEAR (0) or RESIZE_AREA (1), got %r" % (b, interp))
+        if top < 0 or left < 0 or top + nh > Ho or left + nw > Wo:
+            raise ValueError("resize_pad_pairs: image %d: content %d x %d at (%d, %d) does not lie inside the output %d x %d" % (b, nh, nw, top, left, Ho, Wo))
+        if interp == RESIZE_AREA and (nh > h or nw > w):
+            raise ValueError("resize_pad_pairs: image %d: AREA does not enlarge (%r -> %r)" % (b, (h, w), (nh, nw)))
+        recs[b] = L.DykResizePadRec(src_v=v.data_ptr(), src_l=l.data_ptr(), h=h, w=w, nh=nh, nw=nw, top=top, left=left, interp=interp)
+    if out is None:
+        ov = torch.empty((B, 3, Ho, Wo), dtype=torch.uint8, device=dev)
+        ol = torch.empty_like(ov)
+    else:
+        ov, ol = out
+        for t in (ov, ol):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != dev:
+                raise TypeError("resize_pad_pairs: out=(ov, ol), uint8 tensors on the device of the images")
+            if tuple(t.shape) != (B, 3, Ho, Wo) or not t.is_contiguous():
+                raise ValueError("resize_pad_pairs: out tensors are contiguous %r, got %s" % ((B, 3, Ho, Wo), tuple(t.shape)))
+    nbytes = ctypes.sizeof(recs)
+    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:] = np.frombuffer(recs, dtype=np.uint8)
+    drecs = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    drecs.copy_(host, non_blocking=True)
+    d = L.DykResizePadDesc(recs=drecs.data_ptr(), recs_host=ctypes.addressof(recs), dst_v=ov.data_ptr(), dst_l=ol.data_ptr(), B=B, Ho=Ho,
+                           Wo=Wo, layout=_LAYOUTS[layout], color=(ctypes.c_uint8 * 3)(*color))
+    rc = load().dyk_resize_pad_pairs(ctypes.byref(d), _stream())
+    if rc == -1:
+        raise ValueError("resize_pad_pairs: dyk_resize_pad_pairs refused the call (out tensors that overlap each other or an input?)")
+    check(rc, "dyk_resize_pad_pairs")
     return ov, ol

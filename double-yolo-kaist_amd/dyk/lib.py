@@ -285,6 +285,19 @@ class DykAugmentDesc(ctypes.Structure):
                 ("Hc", _i32), ("Wc", _i32), ("Ho", _i32), ("Wo", _i32), ("rects", _vp), ("minv", _vp), ("luts", _vp), ("flip", _vp)]
 
 
+RESIZE_PAD_MAX_SIZE = 16384   # every size of dyk_resize_pad_pairs (include/dyk_hip.h)
+
+
+class DykResizePadRec(ctypes.Structure):
+    _fields_ = [("src_v", _vp), ("src_l", _vp), ("h", _i32), ("w", _i32), ("nh", _i32), ("nw", _i32), ("top", _i32), ("left", _i32),
+                ("interp", _i32), ("reserved", _i32)]
+
+
+class DykResizePadDesc(ctypes.Structure):
+    _fields_ = [("recs", _vp), ("recs_host", _vp), ("dst_v", _vp), ("dst_l", _vp), ("B", _i32), ("Ho", _i32), ("Wo", _i32),
+                ("layout", _i32), ("color", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8 * 5)]
+
+
 _lib = None
 _P = ctypes.POINTER
 
@@ -384,6 +397,7 @@ SIGNATURES = {
     "dyk_cutout_rects": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "dyk_augment_pairs": (_i32, [_P(DykAugmentDesc), _vp]),
     "dyk_augment_pairs_rows": (_i32, [_P(DykAugmentDesc), _i32, _vp]),
+    "dyk_resize_pad_pairs": (_i32, [_P(DykResizePadDesc), _vp]),
 }
 
 

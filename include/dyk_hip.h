@@ -1383,6 +1383,80 @@ int dyk_augment_pairs(const DykAugmentDesc* desc, void* stream);
  * which measures that choice; the output does not depend on it.  DYK_ERR_ARG for rows outside 1..64. */
 int dyk_augment_pairs_rows(const DykAugmentDesc* desc, int32_t rows, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Resize and letterbox of image pairs on the device (reference build_utils/kaist_dataset.py:204-208 the cv2.resize of
+ * load_image, build_utils/img_utils.py:5-53 letterbox, kaist_dataset.py:378-379 BGR HWC -> RGB CHW): dyk_resize_pad_pairs,
+ * ONE launch for both streams of a batch.  The geometry and the label arithmetic stay on the host
+ * (build_utils/letterbox.py); every pixel is made here.
+ *
+ * The resize rule is the classical OpenCV 8-bit resize (modules/imgproc/src/resize.cpp: INTER_LINEAR and INTER_AREA) written
+ * down as this project's own rule.  It is DERIVED, NOT MEASURED: no OpenCV runs where this project runs, and OpenCV builds
+ * with IPP or newer SIMD paths may differ; what is held bit for bit is this text, tests/letterbox_ref.py and its hand-worked
+ * cases.
+ *
+ * Per output image b the two sources (visible, LWIR) share one record: the source size h x w, the resized content size
+ * nh x nw, the place (top, left) of the content in the Ho x Wo output, interp (0 = LINEAR, 1 = AREA) and the two source
+ * addresses.  Sources of one batch may differ in size.  layout 0: a source is planar [3][h][w] and plane c of the output comes
+ * from plane c.  layout 1: a source is interleaved [h][w][3] and plane c of the output comes from channel 2 - c (cv2.imread's
+ * BGR HWC becomes planar RGB).  With S the source plane of output plane c:
+ *     out(b, c, y, x) = color[c]                              outside [top, top+nh) x [left, left+nw)
+ *                       resized S at (y - top, x - left)      inside; a plain copy of S when nh == h and nw == w.
+ *
+ * Scales, both modes, per axis in fp64: inv = (double)n_dst / (double)n_src; scale = 1.0 / inv  (two roundings; not
+ * n_src / n_dst).  rn = round half to even to integer.  Every float and double multiply, add and subtract is an operation of
+ * its own (no fused multiply-add).
+ *
+ * LINEAR.  Per destination column dx: fx = (float)((dx + 0.5) * scale_x - 0.5), computed in fp64 and cast once;
+ *     sx = floor(fx); fx -= sx (fp32);  if sx < 0: sx = 0, fx = 0;  if sx >= w - 1: sx = w - 1, fx = 0;
+ *     a0 = rn((1.f - fx) * 2048.f); a1 = rn(fx * 2048.f);
+ *     D(sy, dx) = S[sy][sx] * a0 + S[sy][sx+1] * a1  (int32);   where sx + 1 >= w:  D = S[sy][sx] * 2048.
+ *   Per destination row dy: fy, sy, b0, b1 the same way but WITHOUT the two edge resets; the two tap rows are
+ *     clamp(sy, 0, h-1) and clamp(sy+1, 0, h-1), the coefficients as computed.
+ *     out = ( ((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2 ) >> 2
+ *   (the form of OpenCV's 8-bit vertical pass; NOT (b0*D0 + b1*D1 + 2^21) >> 22).  When both axes shrink by exactly 2
+ *   (w == 2*nw and h == 2*nh) LINEAR is AREA, as in OpenCV.
+ *
+ * AREA, admitted only when nw <= w and nh <= h.
+ *   (i) w % nw == 0 and h % nh == 0, kx = w / nw, ky = h / nh: sum = int32 sum of the kx x ky block;
+ *       kx == ky == 2: out = (sum + 2) >> 2;  otherwise out = sat_u8(rn(sum * (1.f / (kx*ky)))), the reciprocal formed in fp32,
+ *       one fp32 multiply.
+ *   (ii) otherwise the weighted form.  Per axis and destination index d, in fp64: f1 = d * scale; f2 = f1 + scale;
+ *       cell = min(scale, n_src - f1); s1 = ceil(f1); s2 = min(floor(f2), n_src - 1); s1 = min(s1, s2).  Taps, in this order:
+ *           if s1 - f1 > 1e-3:  (s1 - 1, (float)((s1 - f1) / cell))
+ *           for s1 <= s < s2:   (s, (float)(1.0 / cell))
+ *           if f2 - s2 > 1e-3:  (s2, (float)(min(min(f2 - s2, 1.0), cell) / cell))
+ *       In fp32: for each row tap (sy, beta) in order, buf = the sum over the column taps (sx, alpha) in order of
+ *       (float)S[sy][sx] * alpha, starting from 0.f; acc = beta * buf for the first row tap, acc = acc + beta * buf for the
+ *       following ones; out = sat_u8(rn(acc)).
+ *
+ * recs is a DEVICE array, read by the kernel; recs_host holds the same B records on the host and is validated before the
+ * launch.  No allocation, no synchronisation, no atomics.  DYK_ERR_ARG before the launch: a null descriptor, record array,
+ * destination or source pointer; B, Ho, Wo < 1; any size (B, Ho, Wo, h, w, nh, nw) above 16384; h, w, nh or nw < 1; layout or
+ * interp outside their values; top < 0, left < 0, top + nh > Ho or left + nw > Wo; AREA with nw > w or nh > h; dst_v and
+ * dst_l overlapping, or a destination overlapping a source.  The kernel bounds every tap by the record's h and w and never
+ * reads outside a source described truthfully.
+ * ---------------------------------------------------------------------------------- */
+typedef struct DykResizePadRec {
+    const uint8_t* src_v;   /* device: the visible image of slot b */
+    const uint8_t* src_l;   /* device: the LWIR image of slot b */
+    int32_t h, w;           /* source size */
+    int32_t nh, nw;         /* resized content size */
+    int32_t top, left;      /* where the content sits in the output */
+    int32_t interp;         /* 0 = LINEAR, 1 = AREA */
+    int32_t reserved;       /* 0 */
+} DykResizePadRec;
+typedef struct DykResizePadDesc {
+    const DykResizePadRec* recs;        /* device [B] */
+    const DykResizePadRec* recs_host;   /* host [B], the same records */
+    uint8_t* dst_v;                     /* [B][3][Ho][Wo] */
+    uint8_t* dst_l;                     /* [B][3][Ho][Wo] */
+    int32_t B, Ho, Wo;
+    int32_t layout;                     /* 0 = planar [3][h][w], 1 = interleaved [h][w][3] with the channels reversed */
+    uint8_t color[3];                   /* border value per OUTPUT plane */
+    uint8_t reserved[5];                /* 0 */
+} DykResizePadDesc;
+int dyk_resize_pad_pairs(const DykResizePadDesc* desc, void* stream);
+
 /* Profiling variant of dyk_run_commands: brackets every command with HIP events on `stream`
  * and, after synchronising the stream, writes each command's duration in milliseconds to
  * ms_out[0..n).  Used by bench.py's roofline pass, never in a timed throughput region. */
