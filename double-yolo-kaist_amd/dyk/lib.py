@@ -298,6 +298,23 @@ class DykResizePadDesc(ctypes.Structure):
                 ("layout", _i32), ("color", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8 * 5)]
 
 
+ANCHOR_MAX_K, ANCHOR_MAX_N, ANCHOR_MAX_G, ANCHOR_FIT_ITEM = 32, (1 << 27) - 1, 4096, 1024   # DYK_ANCHOR_* (include/dyk_hip.h)
+
+
+class DykAnchorAssignDesc(ctypes.Structure):
+    _fields_ = [("wh", _vp), ("c", _vp), ("nearest", _vp), ("stats", _vp), ("N", _i32), ("K", _i32), ("elem_bytes", _i32), ("reserved", _i32)]
+
+
+class DykAnchorMedianDesc(ctypes.Structure):
+    _fields_ = [("wh", _vp), ("nearest", _vp), ("c", _vp), ("ws", _vp), ("ws_bytes", _i64), ("N", _i32), ("K", _i32), ("elem_bytes", _i32),
+                ("reserved", _i32)]
+
+
+class DykAnchorFitnessDesc(ctypes.Structure):
+    _fields_ = [("wh", _vp), ("a", _vp), ("ws", _vp), ("fit_boxes", _vp), ("fit_anchors", _vp), ("hit_boxes", _vp), ("hit_anchors", _vp),
+                ("ws_bytes", _i64), ("thr", ctypes.c_double), ("N", _i32), ("K", _i32), ("G", _i32), ("elem_bytes", _i32)]
+
+
 _lib = None
 _P = ctypes.POINTER
 
@@ -398,6 +415,11 @@ SIGNATURES = {
     "dyk_augment_pairs": (_i32, [_P(DykAugmentDesc), _vp]),
     "dyk_augment_pairs_rows": (_i32, [_P(DykAugmentDesc), _i32, _vp]),
     "dyk_resize_pad_pairs": (_i32, [_P(DykResizePadDesc), _vp]),
+    "dyk_anchor_assign": (_i32, [_P(DykAnchorAssignDesc), _vp]),
+    "dyk_anchor_median_ws_bytes": (_i64, [_i32]),
+    "dyk_anchor_median": (_i32, [_P(DykAnchorMedianDesc), _vp]),
+    "dyk_anchor_fitness_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "dyk_anchor_fitness": (_i32, [_P(DykAnchorFitnessDesc), _vp]),
 }
 
 

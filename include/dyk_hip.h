@@ -1457,6 +1457,109 @@ typedef struct DykResizePadDesc {
 } DykResizePadDesc;
 int dyk_resize_pad_pairs(const DykResizePadDesc* desc, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Anchor clustering on the device (reference other_utils/anchor_cluster.py: wh_iou :153, k_means :169, anchor_fitness :199 and
+ * the genetic loop of anchor_cluster :219): dyk_anchor_assign, dyk_anchor_median, dyk_anchor_fitness.  The host side
+ * (other_utils/anchor_cluster.py) keeps the label readers, the random draws and the accept decisions; every N-sized pass is
+ * made here.  What follows is this project's own rule; tests/anchor_ref.py restates it in numpy and the entries are held to
+ * that restatement bit for bit.
+ *
+ * Common.  Boxes wh[N][2] = (w, h) and centres c[K][2] are contiguous, both fp32 (elem_bytes 4) or both fp64 (elem_bytes 8).
+ * 1 <= K <= DYK_ANCHOR_MAX_K, 1 <= N <= DYK_ANCHOR_MAX_N (N < 2^27), 1 <= G <= DYK_ANCHOR_MAX_G.  Every box and every anchor is
+ * finite and > 0.  Every floating-point operation below is rounded on its own: no fused multiply-add, no reassociation.
+ *
+ * dyk_anchor_assign : ONE launch (after a memset of stats).  In the type T of the inputs, per box i and centre k:
+ *     inter = min(w, cw) * min(h, ch)
+ *     iou   = inter / (((w * h) + (cw * ch)) - inter)
+ *     d     = 1 - iou
+ *     nearest[i] = the SMALLEST k that attains the minimum of d (np.argmin; ties that only the rounding of 1 - iou creates
+ *                  count as ties)
+ *   stats[0..K) = counts: the number of i with nearest[i] == k.  Exact.
+ *   stats[K]    = changed: the number of i whose new nearest[i] differs from the value the buffer held before the launch.
+ *   stats[K+1]  = bad: the number of rows i with w or h not finite or not > 0.  Such a row gets nearest[i] = 0 and is counted
+ *                 in counts[0]; a caller that sees bad != 0 has no result.
+ *   Integer atomics only (workgroup partials in LDS, one global integer add per workgroup and non-zero counter): every
+ *   output is a pure function of the inputs.
+ *
+ * dyk_anchor_median : all 2K (cluster k, coordinate j) selections together.  The members of k are the i with
+ *   nearest[i] == k, m of them.  x[0] <= ... <= x[m-1] their wh[i][j] in order:
+ *     m odd  : c[k][j] = x[(m-1)/2]
+ *     m even : c[k][j] = (x[m/2 - 1] + x[m/2]) / 2   in T (one add, one divide)
+ *     m == 0 : c[k][j] is left as it was (a NAMED DEPARTURE from the reference, whose np.median of nothing is NaN)
+ *   Selection is a radix select over the bit pattern (positive finite floats order as unsigned integers), 8 bits per pass
+ *   from the top (4 passes in fp32, 8 in fp64).  A pass is a histogram launch over all boxes (256 integer bins per selection
+ *   in LDS, 16 clusters per launch, added to the workspace with integer atomics) and a pick launch (one workgroup per
+ *   selection takes the digit that holds the rank).  Where the upper middle is not the lower middle's value it is the
+ *   smallest member above it (one more launch over the boxes, an integer minimum); a last launch writes the centres.  The
+ *   kernel boundaries order these launches; nothing is handed over inside one.  Integer counts only: the result is a pure
+ *   function of (wh, nearest).  Each coordinate on its own, as np.median(axis=0).  Values of nearest outside [0, K) belong to
+ *   no cluster.  ws: dyk_anchor_median_ws_bytes(K) bytes, 8-byte aligned (0 for K out of range); its content is scratch.
+ *
+ * dyk_anchor_fitness : two launches (partials over (blocks of boxes) x G, then a fold); no atomics, no in-launch hand-off.
+ *   Boxes fp32 or fp64, promoted exactly to fp64; candidates a[G][K][2] and thr in fp64.  Per candidate g, box i, anchor k,
+ *   coordinate j, all in fp64:
+ *     r = wh[i][j] / a[g][k][j];   q = 1.0 / r  (a second rounded division, NOT a / wh);   m = min(r, q)
+ *     x[i][k] = min(m for j = 0, m for j = 1)
+ *   "boxes"   : b[i] = max over k of x[i][k];  term[i] = b[i] if b[i] > thr else +0.0  (strict);
+ *               fit_boxes[g] = S / (double)N,  hit_boxes[g] = the number of i with b[i] > thr,
+ *     where S is the sum of term[i] in THIS ORDER.  Item p is the boxes [DYK_ANCHOR_FIT_ITEM * p, DYK_ANCHOR_FIT_ITEM * (p+1))
+ *     below N; one workgroup of 256 threads per (item, g).  Thread t adds term[1024 p + t], [.. + t + 256], [.. + t + 512],
+ *     [.. + t + 768] in that order to an accumulator that starts at +0.0 (a box at or past N adds +0.0).  The 64 lanes of a
+ *     wave fold as l += l+32, l+16, l+8, l+4, l+2, l+1; the four waves add as ((w0 + w1) + w2) + w3: the item partial.  Fold:
+ *     one wave per g; lane l adds the partials of items l, l + 64, l + 128, ... in that order to an accumulator that starts at
+ *     +0.0, the lanes fold as above.  Every term is >= +0.0, so the zeros of absent boxes and items change no bit: S is a
+ *     function of (wh, a[g], thr) only, identical from run to run and independent of G and of the grid.
+ *   "anchors" : t[k] = max over i of x[i][k]  (exact in any order);
+ *               fit_anchors[g] = (the sum over k = 0 .. K-1, in that order from +0.0, of t[k] if t[k] > thr else +0.0) / (double)K
+ *               hit_anchors[g] = the number of k with t[k] > thr.  (What the reference's call anchor_fitness(k, wh, thr)
+ *               computes, its arguments being swapped against the definition.)
+ *   ws: dyk_anchor_fitness_ws_bytes(N, G, K) bytes, 8-byte aligned (0 for arguments out of range).
+ *
+ * DYK_ERR_ARG before any launch: a NULL descriptor or pointer, N, K, G out of range, elem_bytes not 4 or 8, a pointer not
+ * aligned to its element (ws: 8 bytes), ws_bytes too small, thr not finite.  No kernel indexes past N, K or G.
+ * ---------------------------------------------------------------------------------- */
+#define DYK_ANCHOR_MAX_K 32
+#define DYK_ANCHOR_MAX_N ((1 << 27) - 1)
+#define DYK_ANCHOR_MAX_G 4096
+#define DYK_ANCHOR_FIT_ITEM 1024
+typedef struct DykAnchorAssignDesc {
+    const void* wh;        /* device [N][2] */
+    const void* c;         /* device [K][2] */
+    int32_t* nearest;      /* device [N]: read (previous assignment), then written */
+    int32_t* stats;        /* device [K + 2]: counts, changed, bad */
+    int32_t N, K;
+    int32_t elem_bytes;    /* 4 = fp32, 8 = fp64 */
+    int32_t reserved;      /* 0 */
+} DykAnchorAssignDesc;
+typedef struct DykAnchorMedianDesc {
+    const void* wh;            /* device [N][2] */
+    const int32_t* nearest;    /* device [N] */
+    void* c;                   /* device [K][2]: written except for empty clusters */
+    void* ws;                  /* device, dyk_anchor_median_ws_bytes(K) bytes */
+    int64_t ws_bytes;
+    int32_t N, K;
+    int32_t elem_bytes;
+    int32_t reserved;
+} DykAnchorMedianDesc;
+typedef struct DykAnchorFitnessDesc {
+    const void* wh;            /* device [N][2] */
+    const double* a;           /* device [G][K][2] */
+    void* ws;                  /* device, dyk_anchor_fitness_ws_bytes(N, G, K) bytes */
+    double* fit_boxes;         /* device [G] */
+    double* fit_anchors;       /* device [G] */
+    int32_t* hit_boxes;        /* device [G] */
+    int32_t* hit_anchors;      /* device [G] */
+    int64_t ws_bytes;
+    double thr;
+    int32_t N, K, G;
+    int32_t elem_bytes;        /* of wh */
+} DykAnchorFitnessDesc;
+int dyk_anchor_assign(const DykAnchorAssignDesc* desc, void* stream);
+int64_t dyk_anchor_median_ws_bytes(int32_t K);
+int dyk_anchor_median(const DykAnchorMedianDesc* desc, void* stream);
+int64_t dyk_anchor_fitness_ws_bytes(int32_t N, int32_t G, int32_t K);
+int dyk_anchor_fitness(const DykAnchorFitnessDesc* desc, void* stream);
+
 /* Profiling variant of dyk_run_commands: brackets every command with HIP events on `stream`
  * and, after synchronising the stream, writes each command's duration in milliseconds to
  * ms_out[0..n).  Used by bench.py's roofline pass, never in a timed throughput region. */
